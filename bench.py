@@ -6,16 +6,25 @@ Headline (BASELINE.json metric): GiB/s of device-resident fp32 sum-reduce of a
 ABI (mi_reduce: inout += in over the whole bucket, inputs resident in HBM).
 
   python bench.py [--gpus N --steps K --warmup W] [--config c2|c3-bf16|c3-fp16|c4|...]
+                   [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+A plain run sets up, warms up, times the K steps, writes its outputs under
+--dump-outputs, and prints the line.  --full adds everything else the
+benchmark measures or checks, each outside the timed region: the launch
+probes, the measured ceilings, the bit-for-bit parity checks (exit 3 on any
+mismatch), the drop-in and host-resident legs, the CPU baseline, the other
+configs' legs, at N > 1 the strong split, the PMC traffic, the memory plan,
+and the side file with the full result.
 With --gpus N > 1 and no launcher (WORLD_SIZE unset), bench.py starts the N
 rank processes itself and relays rank 0's line.
 
 Multi-GPU: the element range is sharded — every rank reduces
 its own 1 GiB bucket shard with no data-path collective ("scaling": "weak");
 torch.distributed is used only for the barrier and the max-over-ranks time.
-Rank 0 prints ONE JSON line.  After the timed region every rank re-fills its
-bucket, runs one more reduce and compares all of its elements bit for bit with
-a torch-computed fold (`parity` in the line; exit 3 on any mismatch).
+Rank 0 prints ONE JSON line.  Under --full, after the timed region every rank
+re-fills its bucket, runs one more reduce and compares all of its elements bit
+for bit with a torch-computed fold (`parity` in the line; exit 3 on any
+mismatch).
 """
 from __future__ import annotations
 
@@ -73,11 +82,19 @@ def parse():
     p.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     p.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                    help="weak: every GPU reduces its own full bucket; strong: one bucket split over the GPUs")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="besides the timed steps: launch probes, measured ceilings, parity checks, the drop-in and "
+                        "host-resident legs, the CPU baseline, the other configs' legs, the strong split at N > 1, "
+                        "PMC traffic, the memory plan and the side file (a plain run does none of them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step left in the reduce's output buffer "
+                        "as DIR/<name>.npy (float32, or float64 for integer types; a fixed, seeded sample of a "
+                        f"buffer over {DUMP_ALL_BYTES >> 20} MiB)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="under --full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="bound on the CPU baseline's work")
-    p.add_argument("--no-host-leg", action="store_true", help="skip the host-resident (PCIe) measurement")
+    p.add_argument("--no-host-leg", action="store_true", help="under --full: skip the host-resident (PCIe) measurement")
     p.add_argument("--no-config-legs", action="store_true",
-                   help="skip the other BASELINE configs' legs (timed launches + full parity) of a c2 run")
+                   help="under --full: skip the other BASELINE configs' legs (timed launches + full parity) of a c2 run")
     p.add_argument("--layout", default="padded", choices=LAYOUTS,
                    help="padded (default): a config's inputs in one allocation, a 2-input config's second operand "
                         f"{PAIR_OFFSET >> 20} MiB after its first; one: consecutive slices of one allocation; "
@@ -86,12 +103,16 @@ def parse():
                    help="process group for the barrier / max-over-ranks only (gloo lets several ranks share "
                         "one GPU when rehearsing the N>1 path)")
     p.add_argument("--detail", default=os.environ.get("MI_BENCH_DETAIL", DETAIL_DEFAULT),
-                   help="side file for the full result (method notes, probe arrays, per-leg ceilings, the CPU "
+                   help="under --full: side file for the full result (method notes, probe arrays, per-leg ceilings, the CPU "
                         "sweep); the stdout line names it")
     return p.parse_args()
 
 
 DETAIL_DEFAULT = "profiles/bench_detail.json"
+DUMP_ALL_BYTES = 32 << 20  # --dump-outputs: a larger output (as float32 / float64) is sampled
+DUMP_EDGE = 4096  # elements at each end of the output that a sample always holds
+DUMP_SAMPLE = 1 << 22  # elements drawn from the whole range besides them
+DUMP_SEED = 0xD0C5
 LINE_LIMIT = 7000  # bytes: under the driver's 8000-character stdout tail, with room to spare
 
 
@@ -146,10 +167,10 @@ def compact_line(full, detail):
         cb["multi_thread"] = _pick(mt, ("threads", "value", "median", "spread", "reps", "cgroup_cpu_quota",
                                         "throttled", "throttled_usec", "psi_cpu_some_us"))
         line["cpu_baseline"] = cb
-    else:
+    elif "cpu_baseline" in full:  # (a plain run, without --full, measures none)
         line["cpu_baseline"] = cpu
-    par = full.get("parity", {})
-    line["parity"] = _pick(par, ("elements", "mismatches"))
+    if "parity" in full:
+        line["parity"] = _pick(full["parity"], ("elements", "mismatches"))
     if full.get("dropin_sync"):
         d = full["dropin_sync"]
         line["dropin_sync"] = dict(_pick(d, ("value", "best")), mismatches=d.get("parity", {}).get("mismatches"))
@@ -179,7 +200,10 @@ def compact_line(full, detail):
             else:  # C1: a host chunk through the drop-in, timed in µs
                 legs[name] = dict(_pick(v, ("median_us", "best_us")), mismatches=mism)
         line["configs"] = legs
-    line["detail"] = detail
+    if detail is not None:
+        line["detail"] = detail
+    if "dumped_outputs" in full:
+        line["dumped_outputs"] = full["dumped_outputs"]
     trimmed = []
     for k in ("host_resident", "strong_split", "memory", "configs"):
         if len(json.dumps(line, separators=(",", ":"))) <= LINE_LIMIT:
@@ -778,13 +802,15 @@ def full_parity(run_once, ins, k, dt, op, flags, seed0, entry):
             "checker": "torch on the device (left fold in the reference's order, IEEE RNE; bits compared)"}
 
 
-def timed_steps(step, steps, warmup, stream, world, probe=10):
+def timed_steps(step, steps, warmup, stream, world, probe=10, after_timed=None):
     """W untimed steps, then exactly K steps bracketed by a barrier and a
     device synchronize on both sides, issued back to back with one HIP event
     pair around all of them on the launch stream: mean launch time = that
     region / K (the kernels plus their dependent-launch gaps, ~2 us each; no
-    per-launch instrumentation inside the timed region).  Afterwards, outside
-    it, `probe` launches each between their own event pair give the spread.
+    per-launch instrumentation inside the timed region).  `after_timed`, if
+    given, is called once the region is closed, while the buffers hold what
+    the last timed step left.  Afterwards, outside the region, `probe`
+    launches each between their own event pair give the spread.
     Returns (wall s, mean launch ms, probe launch ms list)."""
     import torch
     import torch.distributed as dist
@@ -809,6 +835,8 @@ def timed_steps(step, steps, warmup, stream, world, probe=10):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     avg_ms = e0.elapsed_time(e1) / steps
+    if after_timed is not None:
+        after_timed()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(probe)]
     for a, b in ev:
         a.record(stream)
@@ -1218,6 +1246,32 @@ def device_plan(idents):
     return len(c), max(c.values()), len(c) < len(idents)
 
 
+def dump_outputs(out, dirpath, name):
+    """--dump-outputs: the reduce's output buffer `out` (what a caller of the
+    timed path receives: inout after the last timed step) as
+    `dirpath`/`name`.npy, widened exactly: float32 for fp32/bf16/fp16, float64
+    for the integer types (int64 values past 2^53 round).  A buffer over
+    DUMP_ALL_BYTES is sampled: its first and last DUMP_EDGE elements and
+    DUMP_SAMPLE more at indices drawn once from a seeded CPU generator, in
+    ascending order; the same indices in every run of the same arguments."""
+    import numpy as np
+    import torch
+    out = out.reshape(-1)
+    n = out.numel()
+    wide = torch.float32 if out.dtype.is_floating_point else torch.float64
+    if n * (4 if wide is torch.float32 else 8) > DUMP_ALL_BYTES:
+        g = torch.Generator()
+        g.manual_seed(DUMP_SEED)
+        mid = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+        idx = torch.cat([torch.arange(DUMP_EDGE), mid, torch.arange(n - DUMP_EDGE, n)])
+        out = out.index_select(0, idx.to(out.device))
+    a = out.to(wide).cpu().numpy()
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / f"{name}.npy", a)
+    return {"file": f"{name}.npy", "elements": int(a.size), "of": n, "dtype": str(a.dtype)}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1259,7 +1313,7 @@ def main():
     # a gloo group for the ranks that wait while rank 0 times the host cores:
     # they block in a socket read, where an RCCL barrier's stream wait could
     # poll on the CPUs the baseline is measuring
-    idle_pg = dist.new_group(backend="gloo") if world > 1 and args.dist_backend == "nccl" else None
+    idle_pg = dist.new_group(backend="gloo") if args.full and world > 1 and args.dist_backend == "nccl" else None
     pg_world = dist.get_world_size() if world > 1 else 1  # the ranks the process group saw
     ident = device_identity(torch.cuda.current_device())
     idents = [ident]
@@ -1268,7 +1322,7 @@ def main():
         dist.all_gather_object(idents, ident)
     n_devices, ranks_per_device, rehearsal = device_plan(idents)
     pids = [os.getpid()]  # every rank's process: rank 0 keeps them off its timing cores (cpu_baseline)
-    if world > 1:
+    if args.full and world > 1:
         pids = [None] * pg_world
         dist.all_gather_object(pids, os.getpid())
 
@@ -1295,19 +1349,28 @@ def main():
         return m.mi_reduce_multi(arr, k, ins[0].data_ptr(), n, dt, op, flags, sh)
 
     mem_mark("inputs")
-    elapsed, avg_kern_ms, kern_ms = timed_steps(step, args.steps, args.warmup, stream, world)
+    dumped = []
+
+    def dump():  # ins[0]: the reduce's output, as the last timed step left it
+        if args.dump_outputs:
+            dumped.append(dump_outputs(ins[0], args.dump_outputs, "out" if world == 1 else f"out_rank{rank}"))
+
+    elapsed, avg_kern_ms, kern_ms = timed_steps(step, args.steps, args.warmup, stream, world,
+                                                probe=10 if args.full else 0, after_timed=dump)
     elapsed, avg_kern_ms_max = max_over_ranks([elapsed, avg_kern_ms], world, coll_dev)
     mem_mark("timed")
     # the achievable ceiling on these buffers (outside the timed region;
     # overwrites ins[0], which full_parity refills)
-    ceil = measured_ceiling(ins, k, n * es, stream)
+    ceil = measured_ceiling(ins, k, n * es, stream) if args.full else None
     mem_mark("ceiling")
 
     # the whole bucket checked bit for bit, outside the timed region (every
     # rank checks its own; the line reports the sum over ranks)
     seed0 = 0x5EED + 7919 * rank
-    parity = full_parity(lambda: _lib.check(step(), "mi_reduce"), ins, k, dt, op, flags, seed0,
-                         "mi_reduce" if k == 2 else "mi_reduce_multi")
+    parity = None
+    if args.full:
+        parity = full_parity(lambda: _lib.check(step(), "mi_reduce"), ins, k, dt, op, flags, seed0,
+                             "mi_reduce" if k == 2 else "mi_reduce_multi")
 
     units_per_rank = n * es  # bucket bytes this rank reduced per step
     value = total_bytes * args.steps / elapsed / GiB
@@ -1321,7 +1384,7 @@ def main():
     # the same bucket through oneCCL's own entry point: ccl_comp_reduce of the
     # drop-in shim (synchronous, as src/sched calls it) — reported beside `value`
     dropin = None
-    if k == 2:
+    if args.full and k == 2:
         shim = _lib.shim()
         torch.cuda.synchronize()
         tt = []
@@ -1344,21 +1407,22 @@ def main():
     mem_mark("parity + drop-in")
 
     # totals over ranks (each rank checked its own bucket shard)
-    parity["elements"], parity["mismatches"] = (int(x) for x in sum_over_ranks(
-        [parity["elements"], parity["mismatches"]], world, coll_dev))
+    if parity:
+        parity["elements"], parity["mismatches"] = (int(x) for x in sum_over_ranks(
+            [parity["elements"], parity["mismatches"]], world, coll_dev))
     if dropin:
         dp = dropin["parity"]
         dp["elements"], dp["mismatches"] = (int(x) for x in sum_over_ranks(
             [dp["elements"], dp["mismatches"]], world, coll_dev))
 
     host_leg = None
-    if rank == 0 and world == 1 and not args.no_host_leg and k == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_host_leg and k == 2:
         host_leg = host_resident_leg(m, dt, es, op, flags, min(n, (256 << 20) // es))
 
     cpu = None
-    if world > 1:
+    if args.full and world > 1:
         dist.barrier()  # every rank is past its timed region before rank 0 loads the host cores
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(cfg, args.cpu_seconds, pids)
         except Exception as e:  # noqa: BLE001 - a reported baseline never costs the line
@@ -1367,18 +1431,18 @@ def main():
         if world > 1 and "error" not in cpu:
             cpu["note_n_gpus"] = (f"measured on rank 0 after the {world}-rank timed region and a barrier, while the "
                                   "other ranks wait in a gloo barrier; the same bounded sample as at N=1")
-    if world > 1:
+    if args.full and world > 1:
         dist.barrier(group=idle_pg)  # the other ranks wait here, off the CPUs, until rank 0 is done
 
     legs = None
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_config_legs:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.no_config_legs:
         legs = config_legs(m, stream, args.layout)
 
     # BASELINE configs[3] as written at N > 1: one 1 GiB bucket split over the
     # GPUs, beside the weak-scaling `value` (each GPU its own 1 GiB bucket):
     # the 2-input headline bucket and the 8-input fan-in
     strong = None
-    if world > 1 and args.config == "c2":
+    if args.full and world > 1 and args.config == "c2":
         strong = {"c2": strong_split(m, dt, es, op, k, flags, n_total, rank, world, stream, args.steps,
                                      args.warmup, coll_dev, ins=ins, n_devices=n_devices)}
         mem_mark("strong c2")
@@ -1390,10 +1454,10 @@ def main():
         torch.cuda.empty_cache()
         mem_mark("strong c4")
 
-    traffic = pmc_traffic(args.config, traffic_per_launch)
-    mplan = memory_plan(args.config, args.layout, world, rank, args.scaling)
+    traffic = pmc_traffic(args.config, traffic_per_launch) if args.full else None
+    mplan = memory_plan(args.config, args.layout, world, rank, args.scaling) if args.full else None
     peak_dev = torch.cuda.max_memory_allocated()
-    if world > 1:
+    if args.full and world > 1:
         mem_max, = max_over_ranks([peak_dev], world, coll_dev)
         mem_sum, = sum_over_ranks([peak_dev], world, coll_dev)
     else:
@@ -1428,8 +1492,8 @@ def main():
                          "traffic_ratio_to_algorithmic": traffic.get("ratio") if traffic else None,
                          "algorithmic_bytes_per_launch": traffic_per_launch,
                          "avg_kernel_ms": round(avg_kern_ms, 5), "avg_kernel_ms_max_rank": round(avg_kern_ms_max, 5),
-                         "kernel_ms_min": round(min(kern_ms), 5),
-                         "kernel_ms_probe": [round(x, 5) for x in kern_ms],
+                         **({"kernel_ms_min": round(min(kern_ms), 5),
+                             "kernel_ms_probe": [round(x, 5) for x in kern_ms]} if kern_ms else {}),
                          "aggregate": {"achieved": round(agg_achieved, 1), "peak": agg_peak,
                                        "frac": round(agg_achieved / agg_peak, 4), "devices": n_devices,
                                        "note": "all ranks' algorithmic launch bytes / max-over-ranks mean launch "
@@ -1438,9 +1502,12 @@ def main():
                                    "(avg_kernel_ms = that time / K, inter-launch gaps included); kernel_ms_min/_probe: "
                                    "10 launches each between their own event pair, after the timed region",
                          "traffic_source": traffic.get("source") if traffic else None},
-            "cpu_baseline": cpu,
-            "parity": parity,
         }
+        if args.full:
+            out["cpu_baseline"] = cpu
+            out["parity"] = parity
+        if dumped:
+            out["dumped_outputs"] = dumped
         if ceil:
             out["roofline"]["ceiling_TBps"] = ceil["ceiling_TBps"]
             out["roofline"]["frac_of_ceiling"] = round(achieved / 1e3 / ceil["ceiling_TBps"], 4)
@@ -1461,12 +1528,13 @@ def main():
             out["roofline"]["placement_note"] = (
                 f"headline: {args.layout}; 'separate' (one allocation per operand) is the placement oneCCL's "
                 "recv_reduce_entry produces (comm_buf from the schedule's buffer, inout the user's), DESIGN.md §6")
-        out["memory"] = {"planned_peak_bytes_rank0": mplan["peak_bytes"],
-                         "torch_max_allocated_bytes_max_rank": int(mem_max),
-                         "torch_max_allocated_bytes_sum_ranks": int(mem_sum),
-                         "note": "planned = memory_plan() (bench.py, computed without a GPU); measured = "
-                                 "torch.cuda.max_memory_allocated() per rank (the config legs' buffers included at "
-                                 "N = 1)"}
+        if mplan:
+            out["memory"] = {"planned_peak_bytes_rank0": mplan["peak_bytes"],
+                             "torch_max_allocated_bytes_max_rank": int(mem_max),
+                             "torch_max_allocated_bytes_sum_ranks": int(mem_sum),
+                             "note": "planned = memory_plan() (bench.py, computed without a GPU); measured = "
+                                     "torch.cuda.max_memory_allocated() per rank (the config legs' buffers included "
+                                     "at N = 1)"}
         out["wall_s_rank0"] = round(time.perf_counter() - T0, 2)
         if rehearsal:
             out["rehearsal"] = True
@@ -1480,11 +1548,11 @@ def main():
             out["host_resident"] = host_leg
         if legs:
             out["configs"] = legs
-        detail = write_detail(out, args.detail)
+        detail = write_detail(out, args.detail) if args.full else None
         line_out.write_line(json.dumps(compact_line(out, detail), separators=(",", ":")))
     if world > 1:
         dist.destroy_process_group()
-    bad = parity["mismatches"] + (dropin["parity"]["mismatches"] if dropin else 0)
+    bad = (parity["mismatches"] if parity else 0) + (dropin["parity"]["mismatches"] if dropin else 0)
     bad += sum(v["parity"]["mismatches"] for v in (legs or {}).values())
     if bad:
         log(f"PARITY FAILURE: {bad} element(s) differ from the expected result")

@@ -575,3 +575,68 @@ def test_compact_line_keeps_a_failed_cpu_baseline_and_no_legs():
     assert line["cpu_baseline"] == {"error": "OSError: no cores"}
     assert "configs" not in line and "host_resident" not in line and "trimmed" not in line
     assert json.loads(json.dumps(line)) == line
+
+
+def test_full_is_off_by_default_and_dump_outputs_takes_a_dir(monkeypatch):
+    """A plain run does the timed steps only; --full and --dump-outputs are opt-in."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+    # what --dump-outputs writes stays within 64 MB, whole or sampled (8 bytes per element at most)
+    assert bench.DUMP_ALL_BYTES <= 64 << 20 and (2 * bench.DUMP_EDGE + bench.DUMP_SAMPLE) * 8 <= 64 << 20
+
+
+def test_compact_line_of_a_plain_run_keeps_the_contract_keys():
+    """The line of a run without --full: the contract keys and the roofline of
+    the timed region, none of the sections only --full measures, no side file."""
+    full = _canned_full()
+    for k in ("cpu_baseline", "parity", "configs", "host_resident", "dropin_sync", "memory"):
+        full.pop(k, None)
+    line = bench.compact_line(full, None)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert line[k] == full[k], k
+    assert line["roofline"]["frac"] == full["roofline"]["frac"]
+    for k in ("cpu_baseline", "parity", "configs", "host_resident", "dropin_sync", "memory", "detail", "trimmed"):
+        assert k not in line, k
+    assert json.loads(json.dumps(line)) == line
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16", "float16", "int32", "int64"])
+def test_dump_outputs_whole_buffer_is_exact(dtype, tmp_path):
+    """A buffer within DUMP_ALL_BYTES is written whole: float32 for the
+    floating types (bf16/fp16 widen exactly), float64 for the integer ones."""
+    import numpy as np
+    import torch
+    tdt = getattr(torch, dtype)
+    g = torch.Generator().manual_seed(5)
+    t = (torch.rand(1003, generator=g) * 8 - 4).to(tdt) if tdt.is_floating_point else \
+        torch.randint(-2 ** 31, 2 ** 31 - 1, (1003,), generator=g).to(tdt)
+    info = bench.dump_outputs(t, tmp_path / "sub", "out")
+    a = np.load(tmp_path / "sub" / "out.npy")
+    wide = np.float32 if tdt.is_floating_point else np.float64
+    assert a.dtype == wide and a.shape == (1003,)
+    assert np.array_equal(a, t.to(torch.float64).numpy().astype(wide))
+    assert info == {"file": "out.npy", "elements": 1003, "of": 1003, "dtype": np.dtype(wide).name}
+
+
+def test_dump_outputs_samples_a_large_buffer_the_same_way_every_time(tmp_path, monkeypatch):
+    """Past DUMP_ALL_BYTES: both ends and a seeded draw of the rest, in
+    ascending index order, identical from call to call."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_ALL_BYTES", 4000)
+    monkeypatch.setattr(bench, "DUMP_EDGE", 16)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    n = 5001
+    t = torch.arange(n, dtype=torch.float32)  # the value is the index
+    info = bench.dump_outputs(t, tmp_path, "a")
+    bench.dump_outputs(t.clone(), tmp_path, "b")
+    a, b = np.load(tmp_path / "a.npy"), np.load(tmp_path / "b.npy")
+    assert info["elements"] == a.size == 132 and info["of"] == n and a.dtype == np.float32
+    assert np.array_equal(a, b)
+    assert np.array_equal(a[:16], np.arange(16)) and np.array_equal(a[-16:], np.arange(n - 16, n))
+    mid = a[16:-16]
+    assert (np.diff(mid) >= 0).all() and 0 <= mid.min() and mid.max() < n and len(set(mid)) > 50

@@ -21,6 +21,7 @@ reference tree is only read.  Runs where /root/reference exists.
 """
 from __future__ import annotations
 
+import os
 import re
 import shutil
 import subprocess
@@ -30,7 +31,7 @@ import pytest
 
 from tests.test_intree_build import DEFS, REF, ROOT, WARN, _global_defs, _undefs
 
-pytestmark = pytest.mark.skipif(not (REF / "src" / "comp").is_dir(),
+pytestmark = pytest.mark.skipif(not os.path.isdir(REF / "src" / "comp"),
                                 reason="reference tree absent (GPU box): checked in the build container")
 
 PATCHES = sorted((ROOT / "integration").glob("*.patch"))

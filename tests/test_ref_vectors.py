@@ -10,6 +10,7 @@ committed file, so the fixture cannot drift from what the reference computes.
 """
 from __future__ import annotations
 
+import os
 import subprocess
 import json
 from pathlib import Path
@@ -76,7 +77,7 @@ def test_fixture_covers_every_avx512_variant():
     assert native == {2061, 32, 31, 1}  # avx512fp16: 32-wide body, masked tails
 
 
-@pytest.mark.skipif(not REF.is_dir(), reason="reference tree absent (GPU box): the committed fixture is used")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree absent (GPU box): the committed fixture is used")
 def test_fixture_regenerates_from_reference_code():
     """Rebuild oracle/_ref from the reference sources and regenerate every
     vector: identical to the committed fixture."""
@@ -101,7 +102,7 @@ def _has_avx512fp16():
         return False
 
 
-@pytest.mark.skipif(not REF.is_dir() or not _has_avx512fp16(),
+@pytest.mark.skipif(not os.path.isdir(REF) or not _has_avx512fp16(),
                     reason="needs the reference tree and a CPU with AVX512_FP16 (the committed fixture is used)")
 def test_fp16native_fixture_regenerates_from_reference_code():
     """The avx512fp16 vectors: rebuild oracle/_ref/libref_fp16native.so (clang++

@@ -132,9 +132,9 @@ for step in "$@"; do
         policy)
             run policy 300 ./tools/policy_sweep 1024 5 10 ;;
         bench)
-            run bench 600 python bench.py ;;
+            run bench 600 python bench.py --full ;;
         bench3)  # run-to-run spread of the headline in one box
-            for i in 1 2 3; do run "bench_rep$i" 300 python bench.py --no-cpu-baseline --no-host-leg; done ;;
+            for i in 1 2 3; do run "bench_rep$i" 300 python bench.py --full --no-cpu-baseline --no-host-leg; done ;;
         warm)
             run warm 300 python tools/warm_probe.py ;;
         c1)
@@ -165,11 +165,11 @@ for step in "$@"; do
             run coop 600 python tools/dispatch_sweep.py --min-kib 16384 --max-mib 1024 --shares 0.2,0.3,0.4,0.5,0.6 ;;
         dist2)
             run dist2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-                --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo &&
+                --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo --full &&
             run dist2_strong 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-                --master-port 29534 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo --scaling strong ;;
+                --master-port 29534 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo --scaling strong --full ;;
         dist2self)  # bench.py as its own launcher: --gpus 2 with no WORLD_SIZE (both ranks share the box's GPU)
-            run dist2self 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline ;;  # nccl -> gloo on 1 GPU
+            run dist2self 300 python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline ;;  # nccl -> gloo on 1 GPU
         pmcjson)  # the PMC passes of `pmc` (and PMC_CONFIG=c4's) summarised into profiles-ready JSON
             specs="c2=$OUT:3221225472"
             [ -d "$OUT/pmc_c4" ] && specs="$specs c4=$OUT/pmc_c4:9663676416"
@@ -192,13 +192,14 @@ for step in "$@"; do
                 -p no:cacheprovider --timeout 300 --timeout-method thread ;;
         benchall)
             for c in c3-bf16 c3-fp16 c4 c4-bf16acc c5-int32-max c5-int64-prod; do
-                run "bench_$c" 300 python bench.py --config "$c" --no-cpu-baseline --no-host-leg
+                run "bench_$c" 300 python bench.py --config "$c" --full --no-cpu-baseline --no-host-leg
             done ;;
         prof)  # PROF_CONFIG=c4 etc. profiles another bench config
             pc=${PROF_CONFIG:-c2}; pd=prof; [ "$pc" = c2 ] || pd=prof_$pc
             (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
                 -d "$GRAFT_REPO_ROOT/$OUT/$pd" -o bench -- \
                 python3 "$GRAFT_REPO_ROOT/bench.py" --config "$pc" --steps 20 --warmup 5 --no-cpu-baseline --no-host-leg --no-config-legs \
+                --full \
                 > "$GRAFT_REPO_ROOT/$OUT/$pd.out" 2> "$GRAFT_REPO_ROOT/$OUT/$pd.err")
             rc=$?; echo "=== $pd rc=$rc" | tee -a "$OUT/steps.log"
             [ $rc -eq 0 ] || exit $rc ;;
@@ -215,6 +216,7 @@ for step in "$@"; do
                 (cd /tmp && timeout -k 10 300 rocprofv3 --pmc $ctr --output-format csv \
                     -d "$GRAFT_REPO_ROOT/$pdir/pmc_$ctr" -o bench -- \
                     python3 "$GRAFT_REPO_ROOT/bench.py" --config "$pc" --steps 5 --warmup 2 --no-cpu-baseline \
+                    --full \
                     --no-host-leg --no-config-legs > "$GRAFT_REPO_ROOT/$pdir/pmc_$ctr.out" 2> "$GRAFT_REPO_ROOT/$pdir/pmc_$ctr.err")
                 rc=$?; echo "=== pmc $pc $ctr rc=$rc" | tee -a "$OUT/steps.log"
                 [ $rc -eq 0 ] || exit $rc

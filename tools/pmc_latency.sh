@@ -20,6 +20,7 @@ for cfg in c2 c4; do
     d="$GRAFT_REPO_ROOT/$OUT/pmclat_${cfg}_$i"
     (cd /tmp && timeout -s KILL 90 rocprofv3 --pmc $p --output-format csv -d "$d" -o bench -- \
         python3 "$GRAFT_REPO_ROOT/bench.py" --config "$cfg" --steps 5 --warmup 2 --no-cpu-baseline --no-host-leg \
+        --full \
         > "$d.out" 2> "$d.err")
     rc=$?
     echo "pmclat $cfg pass $i ($p) rc=$rc"
