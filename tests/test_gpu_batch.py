@@ -1,6 +1,7 @@
 """mi_reduce_batch: many independent in-place reduces in one dispatch, each
 checked bit-exactly against the oracle's ccl_comp_reduce on its own
-operands (NaN payloads aside).  Descriptor counts cross the 64-per-launch
+operands (NaN payloads included), and every byte of the pool outside the
+outputs must stay as it was.  Descriptor counts cross the 64-per-launch
 split.  Counts run from empty to multi-tile, and each operand has its own
 element offset: common and differing misalignments, plus a byte-misaligned
 fp32 pair that takes the element loop.
@@ -13,7 +14,7 @@ import pytest
 import oracle
 from oneccl_amd import _lib
 from oneccl_amd.comp import F_MINMAX_INOUT_FIRST, bf16_flags
-from tests.util import ALL_DTYPES, BF16, DT_NAME, FP16, FP32, OP_NAME, OPS, assert_same, rand_array
+from tests.util import ALL_DTYPES, BF16, DT_NAME, FP16, FP32, OP_NAME, OPS, assert_same, guard_fill, rand_array
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +22,15 @@ SIZES = [0, 1, 7, 17, 255, 4096, 16384 + 9, 100_003]
 
 
 class Pool:
-    """Slots carved from one device allocation, 256 B apart."""
+    """Slots carved from one device allocation, 256 B apart.  The allocation
+    is filled with seeded random non-zero bytes (a stray store of zeros, what
+    a lane past the end of a tile would write, shows), and `mirror` holds
+    what was put there so that untouched() can compare every byte."""
 
     def __init__(self, nbytes: int):
         import torch
-        self.t = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        self.mirror = guard_fill(nbytes, nbytes)
+        self.t = torch.from_numpy(self.mirror).cuda()
         self.base = self.t.data_ptr()
         self.off = 0
 
@@ -33,12 +38,23 @@ class Pool:
         import torch
         o = self.off + byte_off
         raw = a.view(np.uint8)
+        self.mirror[o:o + raw.size] = raw
         self.t[o:o + raw.size].copy_(torch.from_numpy(raw.copy()))
         self.off = (o + raw.size + 256 + 255) // 256 * 256
         return o
 
     def get(self, o: int, like: np.ndarray) -> np.ndarray:
         return self.t[o:o + like.nbytes].cpu().numpy().view(like.dtype).copy()
+
+    def untouched(self, outputs) -> None:
+        """Every byte outside `outputs` [(offset, nbytes), ...] is what was
+        put there: the gaps between slots, the inputs and the rest of the pool."""
+        changed = self.t.cpu().numpy() != self.mirror
+        for o, nb in outputs:
+            changed[o:o + nb] = False
+        bad = np.flatnonzero(changed)
+        assert bad.size == 0, (f"{bad.size} pool bytes outside the outputs changed; first at "
+                               f"{bad[:5].tolist()}, slots start at {[o for o, _ in outputs][:8]}...")
 
 
 def _flags(dt, variant):
@@ -77,6 +93,7 @@ def _run_batch(dt, op, variant, n, seed, misalign):
     _lib.check(_lib.mi().mi_reduce_batch(descs, n, dt, op, flags, torch.cuda.current_stream().cuda_stream),
                "mi_reduce_batch")
     torch.cuda.synchronize()
+    pool.untouched([(pb, b.nbytes) for (_, b, _), (_, pb) in zip(cases, placed)])
     for i, ((a, b, _), (pa, pb)) in enumerate(zip(cases, placed)):
         exp = b.copy()
         if a.size:
@@ -116,6 +133,7 @@ def test_batch_in_equals_inout_and_byte_misaligned():
     descs = _lib.desc_array([(pool.base + px, pool.base + px, x.size), (pool.base + pa, pool.base + pb, a.size)])
     _lib.check(_lib.mi().mi_reduce_batch(descs, 2, FP32, 0, 0, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
+    pool.untouched([(px, x.nbytes), (pb, b.nbytes)])
     ex = x.copy()
     oracle.comp_reduce(x.copy(), ex, FP32, 0)
     eb = b.copy()

@@ -17,7 +17,7 @@ import pytest
 
 import oracle
 from oneccl_amd import comp
-from tests.util import ALL_DTYPES, BF16, DT_NAME, OP_NAME, OPS, assert_same, rand_array
+from tests.util import ALL_DTYPES, BF16, DT_NAME, OP_NAME, OPS, assert_same, guards_intact, padded, rand_array
 
 pytestmark = pytest.mark.gpu
 
@@ -88,23 +88,21 @@ def test_random_dispatch_case(case, env):
         oracle.batch_reduce(np.concatenate(ins), [j * n for j in range(k)], n, exp, dt, op, keep, int(b_impl),
                             int(f_impl))
     # one host buffer holding every input back to back at an element offset
-    packed = np.zeros(off + nin * n + 16, ins[0].dtype)
-    for j in range(nin):
-        packed[off + j * n:off + (j + 1) * n] = ins[j]
-    acc = np.zeros(off + n + 16, ins[0].dtype)
-    acc[off:off + n] = ins[0]
+    # (the offset and the 16 spare elements of both buffers hold seeded random non-zero bytes)
+    all_in = np.concatenate(ins)
+    seed_in, seed_acc = 5_000_000 + 2 * i, 5_000_001 + 2 * i
+    packed = padded(all_in, 16, off, seed_in)
+    acc = padded(ins[0], 16, off, seed_acc)
     if pinned:
         tp = torch.from_numpy(packed.view(np.uint8).copy()).pin_memory()
         ta = torch.from_numpy(acc.view(np.uint8).copy()).pin_memory()
         p_in, p_acc = tp.data_ptr() + off * es, ta.data_ptr() + off * es
-
-        def read():
-            return ta.numpy().view(exp.dtype)[off:off + n].copy()
+        packed, acc = tp.numpy().view(exp.dtype), ta.numpy().view(exp.dtype)  # the pinned memory itself
     else:
         p_in, p_acc = packed.ctypes.data + off * es, acc.ctypes.data + off * es
 
-        def read():
-            return acc[off:off + n].copy()
+    def read():
+        return acc[off:off + n].copy()
     dtype, red = comp.datatype(dt), comp.reduction(op)
     if k == 1:
         src = p_in + n * es  # input 1
@@ -123,3 +121,6 @@ def test_random_dispatch_case(case, env):
         else:
             comp.comp_batch_reduce(p_in, offsets, n, p_acc, dtype, red, keep)
     assert_same(read(), exp, dt, f"case {case}")
+    guards_intact(acc, ins[0], off, seed_acc, f"case {case}: inout")
+    assert_same(packed[off:off + nin * n], all_in, dt, f"case {case}: inputs modified")
+    guards_intact(packed, all_in, off, seed_in, f"case {case}: inputs")

@@ -16,7 +16,8 @@ import pytest
 import oracle
 from oneccl_amd import _lib
 from oneccl_amd.comp import F_ACC_FP32, F_BF16_RNE, F_MINMAX_INOUT_FIRST, bf16_flags
-from tests.util import ALL_DTYPES, BF16, DT_NAME, FP16, OP_NAME, OPS, assert_same, from_dev, rand_array, to_dev
+from tests.util import (ALL_DTYPES, BF16, DT_NAME, FP16, OP_NAME, OPS, assert_same, from_dev, guard_fill,
+                        guards_intact, padded, rand_array, to_dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -66,20 +67,25 @@ def test_random_case(case):
             flags = F_MINMAX_INOUT_FIRST if dt == FP16 else 0
             bimpl = oracle.BF16_AVX512BF
         exp = oracle.fanin(ins, dt, op, bimpl, oracle.FP16_AVX512F)
-    holders = [to_dev(x, pad_elems=16, offset_elems=offs[j]) for j, x in enumerate(ins)]
+    # the offset and pad regions of every operand hold their own random non-zero bytes
+    gseed = [3_000_000 + 32 * i + j for j in range(k + 1)]
+    holders = [to_dev(x, pad_elems=16, offset_elems=offs[j], guard_seed=gseed[j]) for j, x in enumerate(ins)]
     if inplace:
-        to, po, off_o = holders[0][0], holders[0][1], offs[0]
+        to, po, off_o, seed_o = holders[0][0], holders[0][1], offs[0], gseed[0]
     else:
-        off_o = offs[k]
-        to, po = to_dev(np.zeros_like(ins[0]), pad_elems=16, offset_elems=off_o)
+        off_o, seed_o = offs[k], gseed[k]
+        noise = guard_fill(ins[0].nbytes, seed_o + 16).view(ins[0].dtype)  # the output starts as noise, not zeros
+        to, po = to_dev(noise, pad_elems=16, offset_elems=off_o, guard_seed=seed_o)
     arr = _lib.void_ptr_array([p for _, p in holders])
     _lib.check(_lib.mi().mi_reduce_multi(arr, k, po, n, dt, op, flags, torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     if n:
         assert_same(from_dev(to, ins[0], off_o), exp, dt, f"case {case}")
+    guards_intact(to, ins[0], off_o, seed_o, f"case {case}: output")
     for j, (t, _) in enumerate(holders):  # inputs other than the in-place accumulator are untouched
         if not (inplace and j == 0):
             assert_same(from_dev(t, ins[j], offs[j]), ins[j], dt, f"input {j} modified")
+            guards_intact(t, ins[j], offs[j], gseed[j], f"case {case}: input {j}")
 
 
 def _sync_cases():
@@ -116,26 +122,35 @@ def test_random_sync_case(case):
     es = ins[0].itemsize
     keep = []
 
-    def place(x, kind, off):
-        raw = np.zeros(x.size + off + 16, x.dtype)
-        raw[off:off + x.size] = x
+    def place(x, kind, off, gseed):
+        """Returns (pointer, read the operand back, check its guards): the
+        offset and pad regions hold seeded random non-zero bytes."""
         if kind == 0:
-            t, p = to_dev(x, pad_elems=16, offset_elems=off)
+            t, p = to_dev(x, pad_elems=16, offset_elems=off, guard_seed=gseed)
             keep.append(t)
-            return p, (lambda: from_dev(t, x, off))
+            return p, (lambda: from_dev(t, x, off)), (lambda w: guards_intact(t, x, off, gseed, w))
+        raw = padded(x, 16, off, gseed)
         if kind == 1:
             h = torch.from_numpy(raw.view(np.uint8).copy()).pin_memory()
             keep.append(h)
-            return h.data_ptr() + off * es, (lambda: h.numpy().view(x.dtype)[off:off + x.size].copy())
+            return (h.data_ptr() + off * es, (lambda: h.numpy().view(x.dtype)[off:off + x.size].copy()),
+                    (lambda w: guards_intact(h.numpy(), x, off, gseed, w)))
         keep.append(raw)
-        return raw.ctypes.data + off * es, (lambda: raw[off:off + x.size].copy())
+        return (raw.ctypes.data + off * es, (lambda: raw[off:off + x.size].copy()),
+                (lambda w: guards_intact(raw, x, off, gseed, w)))
 
-    placed = [place(x, kinds[j], offs[j]) for j, x in enumerate(ins)]
+    placed = [place(x, kinds[j], offs[j], 4_000_000 + 32 * i + j) for j, x in enumerate(ins)]
     if inplace:
-        po, read = placed[0]
+        po, read, out_guards = placed[0]
     else:
-        po, read = place(np.zeros_like(ins[0]), kinds[k], offs[k])
-    arr = _lib.void_ptr_array([p for p, _ in placed])
+        noise = guard_fill(ins[0].nbytes, 4_000_000 + 32 * i + 24).view(ins[0].dtype)  # not zeros
+        po, read, out_guards = place(noise, kinds[k], offs[k], 4_000_000 + 32 * i + k)
+    torch.cuda.synchronize()  # the device operands are in place before the library's own streams read them
+    arr = _lib.void_ptr_array([p for p, _, _ in placed])
     _lib.check(_lib.mi().mi_reduce_multi_sync(arr, k, po, n, dt, op, flags, -1))
     if n:
         assert_same(read(), exp, dt, f"case {case}")
+    out_guards(f"case {case}: output")
+    for j, (_, _, guards) in enumerate(placed):
+        if not (inplace and j == 0):
+            guards(f"case {case}: input {j}")

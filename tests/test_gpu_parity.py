@@ -1,8 +1,8 @@
 """GPU parity: the HIP kernels (through the C ABI, include/mi_reduce.h) against
 the CPU oracle (oracle/, a restatement of oneCCL src/comp) on the same seeded
-inputs.  Bar: bit-exact for every dtype and op (floating point: NaN payloads
-excepted — two NaNs compare equal — because x86 and CDNA produce different
-default NaNs; NaN-ness itself must match).
+inputs.  Bar: bit-exact for every dtype and op, NaN payloads included
+(tests/util.py assert_same: the kernels restate x86's NaN rules, which the
+reference's own compiled code pins, rather than take CDNA's default NaN).
 """
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ import oracle
 from oneccl_amd import _lib
 from oneccl_amd.comp import F_ACC_FP32, F_BF16_RNE, F_BF16_TAIL_TRUNC16, F_MINMAX_INOUT_FIRST, bf16_flags
 from tests.util import (ALL_DTYPES, BF16, DT_NAME, FP16, FP32, FP64, INT_DTYPES, OP_NAME, OPS, assert_same,
-                        from_dev, rand_array, to_dev)
+                        from_dev, guards_intact, rand_array, to_dev)
 
 pytestmark = pytest.mark.gpu
 
@@ -121,16 +121,19 @@ def test_differing_misalignment_fanin(dt, op, k, inplace, unaligned_mode):
     var = VARIANTS[dt][-1]
     ins = [rand_array(dt, n, seed=1200 + 31 * j + dt, op=op) for j in range(k)]
     exp = oracle.fanin(ins, dt, op, var[2], var[3])
-    holders = [to_dev(x, pad_elems=16, offset_elems=(j * 3 + 1) % 7) for j, x in enumerate(ins)]
+    holders = [to_dev(x, pad_elems=16, offset_elems=(j * 3 + 1) % 7, guard_seed=100 + j) for j, x in enumerate(ins)]
     if inplace:
-        to, po, off_o = holders[0][0], holders[0][1], 1
+        to, po, off_o, seed_o = holders[0][0], holders[0][1], 1, 100
     else:
-        off_o = 2
-        to, po = to_dev(np.zeros_like(ins[0]), pad_elems=16, offset_elems=off_o)
+        off_o, seed_o = 2, 99
+        to, po = to_dev(np.ones_like(ins[0]), pad_elems=16, offset_elems=off_o, guard_seed=seed_o)
     arr = _lib.void_ptr_array([p for _, p in holders])
     _lib.check(_lib.mi().mi_reduce_multi(arr, k, po, n, dt, op, var[1], _stream()))
     _sync()
     assert_same(from_dev(to, ins[0], off_o), exp, dt)
+    guards_intact(to, ins[0], off_o, seed_o, "output")  # the random non-zero pads around every operand
+    for j, (t, _) in enumerate(holders):
+        guards_intact(t, ins[j], (j * 3 + 1) % 7, 100 + j, f"input {j}")
 
 
 @pytest.mark.parametrize("dt,op", [(FP32, 0), (FP32, 3), (BF16, 0), (4, 1), (FP16, 2)])

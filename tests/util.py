@@ -112,14 +112,37 @@ def assert_same(got: np.ndarray, exp: np.ndarray, dtype: int, what: str = "", na
 _SIGNED = {1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}
 
 
-def to_dev(a: np.ndarray, pad_elems: int = 0, offset_elems: int = 0):
-    """Copy to a fresh device buffer; returns (tensor_holder, device_ptr).
-    `offset_elems` shifts the data inside the buffer to test misaligned
-    pointers."""
-    import torch
-    es = a.itemsize
+def guard_fill(nbytes: int, guard_seed: int) -> np.ndarray:
+    """Seeded random bytes in 1..254: a canary with no zero byte, so that a
+    stray store of zeros (a lane past the end that loaded zeros) shows."""
+    return np.random.default_rng(guard_seed).integers(1, 255, nbytes, dtype=np.uint8)
+
+
+def padded(a: np.ndarray, pad_elems: int = 0, offset_elems: int = 0, guard_seed=None) -> np.ndarray:
+    """`a` with `offset_elems` elements in front and `pad_elems` behind:
+    zeros, or guard_fill(guard_seed) bytes."""
     raw = np.zeros(a.size + pad_elems + offset_elems, a.dtype)
     raw[offset_elems:offset_elems + a.size] = a
+    if guard_seed is not None:
+        front, back = _guard_regions(a.itemsize, pad_elems, offset_elems, guard_seed)
+        raw[:offset_elems] = front.view(a.dtype)
+        raw[offset_elems + a.size:] = back.view(a.dtype)
+    return raw
+
+
+def _guard_regions(es: int, pad_elems: int, offset_elems: int, guard_seed: int):
+    fill = guard_fill((offset_elems + pad_elems) * es, guard_seed)
+    return fill[:offset_elems * es], fill[offset_elems * es:]
+
+
+def to_dev(a: np.ndarray, pad_elems: int = 0, offset_elems: int = 0, guard_seed=None):
+    """Copy to a fresh device buffer; returns (tensor_holder, device_ptr).
+    `offset_elems` shifts the data inside the buffer to test misaligned
+    pointers.  With `guard_seed` the pad and offset regions hold seeded random
+    non-zero bytes instead of zeros; guards_intact() checks them afterwards."""
+    import torch
+    es = a.itemsize
+    raw = padded(a, pad_elems, offset_elems, guard_seed)
     t = torch.from_numpy(raw.view(_SIGNED[es])).cuda()
     return t, t.data_ptr() + offset_elems * es
 
@@ -127,6 +150,43 @@ def to_dev(a: np.ndarray, pad_elems: int = 0, offset_elems: int = 0):
 def from_dev(t, like: np.ndarray, offset_elems: int = 0) -> np.ndarray:
     host = t.cpu().numpy().view(like.dtype)
     return host[offset_elems:offset_elems + like.size].copy()
+
+
+def guards_intact(t, like: np.ndarray, offset_elems: int, guard_seed: int, what: str = "") -> None:
+    """The offset and pad regions of a buffer made by to_dev(like, ...,
+    guard_seed=guard_seed) (or its host counterpart from padded(): a numpy
+    array or a pinned tensor) still hold their fill."""
+    total = t.size if isinstance(t, np.ndarray) else t.numel()
+    esz = t.itemsize if isinstance(t, np.ndarray) else t.element_size()
+    n_lo, n_hi = offset_elems * like.itemsize // esz, (offset_elems + like.size) * like.itemsize // esz
+    flat = t.reshape(-1)
+
+    def region(a, b):  # only the guards travel back from the device
+        part = flat[a:b]
+        return (part if isinstance(part, np.ndarray) else part.cpu().numpy()).view(np.uint8)
+
+    pad_elems = (total * esz) // like.itemsize - offset_elems - like.size
+    front, back = _guard_regions(like.itemsize, pad_elems, offset_elems, guard_seed)
+    for got, fill, side in ((region(0, n_lo), front, "before the operand"), (region(n_hi, total), back, "after its end")):
+        bad = np.flatnonzero(got != fill)
+        if bad.size:
+            b = int(bad[0])
+            d = got.size - b if side.startswith("before") else b
+            raise AssertionError(f"{what}: {bad.size} guard bytes {side} changed; first {d} bytes {side}: "
+                                 f"{int(fill[b]):#04x} -> {int(got[b]):#04x}")
+
+
+def convert_expected(src: np.ndarray, sdt: int, ddt: int, flags: int) -> np.ndarray:
+    """The oracle's fp32 <-> bf16 / fp16 array conversion under mi_convert's
+    flags (0x2 RNE, 0x8 the truncated count % 16 tail)."""
+    n = src.size
+    if sdt == FP32 and ddt == BF16:
+        rne, tail = bool(flags & 0x2), bool(flags & 0x8)
+        lim = (n // 16) * 16 if (rne and tail) else (n if rne else 0)
+        return np.concatenate([oracle.f32_to_bf16(src[:lim], True), oracle.f32_to_bf16(src[lim:], False)])
+    if sdt == FP32:
+        return oracle.f32_to_fp16(src)
+    return oracle.bf16_to_f32(src) if sdt == BF16 else oracle.fp16_to_f32(src)
 
 
 def wait_os_threads_gone(native_ids, timeout=60.0):
