@@ -125,6 +125,46 @@ int mi_reduce_out(const void* in1, const void* in2, void* out, size_t count,
 int mi_reduce_multi(const void* const* inputs, int k, void* out, size_t count,
                     int dtype, int op, unsigned flags, void* stream);
 
+/* Fold k inputs once and write the result to m outputs, in one pass:
+ * acc = inputs[0]; acc = op(inputs[j], acc) for j = 1..k-1 (the fold of
+ * mi_reduce_multi, same flags, same bits); then outs[i][e] = acc[e] for every
+ * i < m.  1 <= k <= MI_MAX_INPUTS, 1 <= m <= MI_MAX_INPUTS.  Asynchronous on
+ * `stream`; device pointers or device-visible pinned host pointers.
+ * The step that completes an allreduce on the GPU.  The reference has it as
+ * allreduce_kernel_<dtype>_<op> (out = peer_out = op(in, peer_in),
+ * src/kernels/kernels.cl:190-217, launched from src/sched/entry/ze/allreduce/
+ * ze_onesided_allreduce_entry.cpp:70-80) and, in the all-to-all allreduce, as
+ * reduce_monolithic_kernel_N (kernels.cl:269-421) followed by
+ * write_monolithic_kernel_N (kernels.cl:424-560,
+ * ze_a2a_allgatherv_entry.cpp:535).  Against mi_reduce_multi plus m - 1
+ * mi_copy calls it moves k + m buffer-sized streams instead of k + 2m - 1,
+ * in one dispatch instead of m.
+ *   Every output holds exactly the bytes mi_reduce_multi(inputs, k, out, ...)
+ * would have written, for every dtype, op and MI_F_* variant.  m = 1 is
+ * mi_reduce_multi.  k = 1 is the pure fan-out (under MI_F_ACC_FP32 what
+ * mi_reduce_multi does for k = 1, then the fan-out).
+ *   Aliasing: an output may be exactly one of the inputs (the same address;
+ * any input, any number of outputs; outs[i] == inputs[i] for all i with
+ * k == m is the in-place one-shot allreduce).  That is safe on every path:
+ * the vector grid is the outputs' common 16-byte grid, an input that is an
+ * output sits on it, so each lane loads exactly the bytes it later stores,
+ * and each lane has issued all k loads for its vector before its first
+ * store (the NaN refold works on the loaded registers, it does not load
+ * again).  Refused with MI_E_INVALID and a message naming the operands,
+ * before any HIP call: two outputs whose byte ranges overlap (equal ones
+ * included), an output that overlaps an input without being equal to it, a
+ * NULL entry, k or m out of range, a bad dtype or op.  count == 0 returns 0
+ * after those checks.  Outputs at differing misalignments mod 16 take the
+ * element loop (same bits).  Captures into a HIP graph as one kernel node.
+ *   Not provided: a _sync, staged or pageable form (a pageable operand is
+ * refused as by mi_reduce_multi), a request form, a drop-in C++ symbol or a
+ * patch under integration/ (the reference's callers are its Level Zero
+ * entries).  Destinations on a peer GPU over xGMI are ordinary device
+ * pointers once peer access is enabled, but have not been run: every test
+ * places all operands on one device.                                       */
+int mi_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m,
+                    size_t count, int dtype, int op, unsigned flags, void* stream);
+
 /* n independent mi_reduce calls in one dispatch: descs[i].inout =
  * op(descs[i].in, descs[i].inout) over descs[i].count elements, all with one
  * dtype / op / flags.  Results are those of the n mi_reduce calls in any
@@ -373,8 +413,16 @@ int mi_get_residency(int device, int k, int* waves_per_cu, unsigned* lds_bytes);
  * waves_per_cu 1..32 (the reservation is 128 / waves_per_cu whole LDS
  * granules, so the residency achieved is one of 32, 25, 21, 18, 16, 14, 12,
  * 11, 10, 9, 8, ...), 0 = back to the plan.
- * tools/residency_ab.py A/Bs the plan against other residencies with it.  */
+ * tools/residency_ab.py A/Bs the plan against other residencies with it.
+ * A mi_reduce_bcast launch of k inputs and m >= 2 outputs is planned by its
+ * streams in flight per wave, s = min(k + m - 1, 16): the fan-in's plan for
+ * s inputs up to 12, 6 waves above; mi_set_residency(s, ...) overrides it. */
 int mi_set_residency(int k, int waves_per_cu);
+/* Store policy of mi_reduce_bcast's vector stores (tuning knob): 1 (default)
+ * = sc1 + nt, as the 2-input kernel stores (the line leaves L2 as it is
+ * written); 0 = nt, as the fan-in stores.  Returns the previous setting.
+ * tools/bcast_sweep.py measured both.                       */
+int mi_set_bcast_store(int sc1);
 /* Override the grid cap (tuning knob; env MI_REDUCE_MAX_BLOCKS).  Under a
  * cap the reduce, copy and conversion kernels stride over the buffer.     */
 int mi_set_max_blocks(int max_blocks);

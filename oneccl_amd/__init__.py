@@ -21,6 +21,7 @@ from .comp import (  # noqa: F401
     fp16_impl,
     impl_types,
     reduce,
+    reduce_bcast,
     reduce_multi,
     reduce_out,
     reduction,
@@ -29,4 +30,4 @@ from .comp import (  # noqa: F401
     shard_range,
 )
 
-__version__ = "0.1.0"
+__version__ = "0.1.1"

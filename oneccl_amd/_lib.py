@@ -40,6 +40,8 @@ MI_API = [
     ("mi_reduce", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint, c_void_p]),
     ("mi_reduce_out", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint, c_void_p]),
     ("mi_reduce_multi", c_int, [POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_uint, c_void_p]),
+    ("mi_reduce_bcast", c_int, [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_size_t, c_int, c_int, c_uint,
+                                c_void_p]),
     ("mi_reduce_batch", c_int, [POINTER(MiReduceDesc), c_int, c_int, c_int, c_uint, c_void_p]),
     ("mi_reduce_sync", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint, c_int]),
     ("mi_reduce_multi_sync", c_int, [POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_uint, c_int]),
@@ -85,6 +87,7 @@ MI_API = [
     ("mi_get_residency", c_int, [c_int, c_int, POINTER(c_int), POINTER(c_uint)]),
     ("mi_set_max_blocks", c_int, [c_int]),
     ("mi_set_residency", c_int, [c_int, c_int]),
+    ("mi_set_bcast_store", c_int, [c_int]),
     ("mi_set_host_mode", c_int, [c_int]),
     ("mi_set_sync_mode", c_int, [c_int]),
     ("mi_set_unaligned_vectors", c_int, [c_int]),

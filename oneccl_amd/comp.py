@@ -162,6 +162,29 @@ def reduce_multi(inputs: Sequence, out, op: reduction = reduction.sum, flags: Op
                                _stream_handle(stream)), "mi_reduce_multi")
 
 
+def reduce_bcast(inputs: Sequence, outs: Sequence, op: reduction = reduction.sum, flags: Optional[int] = None,
+                 stream=None) -> None:
+    """Every tensor of `outs` = the left fold over `inputs` (as reduce_multi),
+    folded once and written to all of them in one pass (mi_reduce_bcast).  An
+    output may be one of the inputs; two outputs may not overlap."""
+    inputs, outs = list(inputs), list(outs)
+    if not inputs or not outs:
+        raise ValueError("reduce_bcast needs at least one input and one output")
+    t0 = inputs[0]
+    for t in inputs + outs:
+        if t.dtype != t0.dtype:
+            raise TypeError(f"all tensors must have one dtype ({t.dtype} against {t0.dtype})")
+        if t.device != t0.device:
+            raise ValueError(f"all tensors must be on one device ({t.device} against {t0.device})")
+        if t.numel() != t0.numel():
+            raise ValueError(f"all tensors must have the same numel ({t.numel()} against {t0.numel()})")
+    dt, count = _dev_args(inputs + outs, None)
+    f = reference_flags(dt) if flags is None else flags
+    check(mi().mi_reduce_bcast(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs),
+                               void_ptr_array([t.data_ptr() for t in outs]), len(outs), count, int(dt), int(op), f,
+                               _stream_handle(stream)), "mi_reduce_bcast")
+
+
 # ---- the drop-in shim (synchronous, host or device pointers) ------------
 
 def comp_reduce(in_ptr: int, count: int, inout_ptr: int, dtype: datatype, op: reduction) -> Optional[int]:
@@ -256,6 +279,7 @@ def shard_range(count: int, rank: int, world: int, align: int = 256) -> tuple[in
 
 
 __all__ = ["reduction", "datatype", "bf16_impl", "fp16_impl", "reduce", "reduce_out", "reduce_multi",
+           "reduce_bcast",
            "comp_reduce", "comp_reduce_start", "comp_batch_reduce_start", "comp_request", "comp_batch_reduce", "comp_copy", "reduction_to_str", "impl_types", "env_reload",
            "shard_range", "bf16_flags", "fp16_flags", "reference_flags", "F_MINMAX_INOUT_FIRST", "F_BF16_RNE",
            "F_ACC_FP32", "F_BF16_TAIL_TRUNC16", "DTYPE_SIZE", "_lib"]

@@ -158,6 +158,7 @@ typedef hipError_t (*LaunchFn)(dim3, hipStream_t, const KArgs&);
 typedef hipError_t (*LaunchFanFn)(hipStream_t, const KArgs&, unsigned lds);
 typedef hipError_t (*Launch2Fn)(dim3, hipStream_t, const R2Args&, unsigned lds);
 typedef hipError_t (*LaunchBFn)(dim3, hipStream_t, const BArgs&, unsigned lds);
+typedef hipError_t (*LaunchBcFn)(unsigned stride_blocks, hipStream_t, const BCArgs&, unsigned lds);
 
 // Lean 2-input kernel shape: one 16-byte vector per lane, one-wave (64-lane)
 // tiles, 21 waves resident per CU (capped by idle LDS, as the fan-in below).
@@ -285,14 +286,39 @@ hipError_t launch_fan(hipStream_t s, const KArgs& a, unsigned lds) {
     return hipGetLastError();
 }
 
+// mi_reduce_bcast.  stride_blocks = 0: one 64-vector tile per block (8 input
+// slots for k <= 8, else 16), capped by `lds` like the fan-in.  Otherwise the
+// grid-stride form with that many blocks of kBlock lanes (a grid cap, or the
+// element loop).
+constexpr int kBcastBlock = 64;
+
+template <typename Tag, int OP, unsigned V>
+hipError_t launch_bcast(unsigned stride_blocks, hipStream_t s, const BCArgs& a, unsigned lds) {
+    if (stride_blocks) {
+        hipLaunchKernelGGL((bcast_stride_kernel<Tag, OP, V, kBlock>), dim3(stride_blocks), dim3(kBlock), 0,
+                           s, a);
+        return hipGetLastError();
+    }
+    constexpr int B = kBcastBlock;
+    const uint64_t blocks = std::max<uint64_t>((a.nvec + B - 1) / B, 1);
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (a.k <= 8)
+        hipLaunchKernelGGL((bcast_kernel<Tag, OP, V, B, 8>), dim3((unsigned)blocks), dim3(B), lds, s, a);
+    else
+        hipLaunchKernelGGL((bcast_kernel<Tag, OP, V, B, kMaxInputs>), dim3((unsigned)blocks), dim3(B), lds, s,
+                           a);
+    return hipGetLastError();
+}
+
 // general: any K (runtime), grid-stride, also the element loop for operands
 // with different misalignments; lean: K = 2 with a common alignment; fan:
-// any other K with a common alignment
+// any other K with a common alignment; bcast: the fold written to M outputs
 struct Kern {
     LaunchFn general = nullptr;
     Launch2Fn lean = nullptr;
     LaunchFanFn fan = nullptr;
     LaunchBFn batch = nullptr;
+    LaunchBcFn bcast = nullptr;
 };
 
 template <typename Tag, int OP, unsigned V>
@@ -315,6 +341,7 @@ Kern entry() {
         k.lean = &launch_lean<Tag, OP, V>;
         k.fan = &launch_fan<Tag, OP, V>;
         k.batch = &launch_batch<Tag, OP, V>;
+        k.bcast = &launch_bcast<Tag, OP, V>;
     }
     return k;
 }
@@ -633,6 +660,154 @@ int launch_reduce(const void* const* inputs, int k, void* out, size_t count, int
             if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;  // grid-stride covers the rest
             e = kern.general(dim3((unsigned)blocks), stream, a);
         }
+    }
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// fold once, write to m outputs (mi_reduce_bcast)
+// ---------------------------------------------------------------------------
+// Store policy of the fan-out's vector stores: 1 = sc1 + nt (as the 2-input
+// kernel: the line leaves L2 as it is written), 0 = nt (as the fan-in).
+// sc1 + nt ran 0.7-2.8 % faster at every streaming shape measured and the same
+// at 256 KiB (tools/bcast_sweep.py --store, profiles/reduce_bcast/).
+// mi_set_bcast_store switches it.
+std::atomic<int> g_bcast_store{1};
+
+// Waves per CU of the one-wave fan-out tiles.  Each wave keeps k loads and
+// then m stores in flight, so a launch is planned by its streams,
+// min(k + m - 1, 16), and mi_set_residency of that count overrides the plan.
+// The fan-in's plan for as many inputs was the fastest at 3 streams (16
+// waves) and 7 (9 waves); at 15 streams 6 waves, not the fan-in's 5: bf16
+// 4.8 % faster there, fp32 1.4 % slower (tools/bcast_sweep.py --residency,
+// profiles/reduce_bcast/).  Only those three stream counts were swept.
+int bcast_streams(int k, int m) { return std::min(k + m - 1, MI_MAX_INPUTS); }
+
+int bcast_planned_waves(int k, int m) {
+    const int s = bcast_streams(k, m);
+    const int o = g_residency_override[s].load(std::memory_order_relaxed);
+    if (o > 0) return o;
+    return s > 12 ? 6 : fan_waves_per_cu(s);
+}
+
+// Every refusal that needs no device, before any HIP call: the ranges of two
+// outputs may not overlap (equal ones included: which store lands last would
+// be the only difference, but a caller passing one buffer twice has miscounted
+// its ranks), and an output may overlap an input only by being it.
+int check_bcast_args(const void* const* inputs, int k, void* const* outs, int m, size_t count, size_t es) {
+    char msg[160];
+    for (int i = 0; i < k; i++)
+        if (!inputs[i]) {
+            snprintf(msg, sizeof(msg), "inputs[%d] is NULL", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    for (int i = 0; i < m; i++)
+        if (!outs[i]) {
+            snprintf(msg, sizeof(msg), "outs[%d] is NULL", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    if (count == 0) return 0;
+    if (count > UINTPTR_MAX / es) return fail(MI_E_INVALID, "count overflows the address space");
+    const uintptr_t nb = count * es;
+    for (int i = 0; i < k; i++)
+        if (nb > UINTPTR_MAX - reinterpret_cast<uintptr_t>(inputs[i])) {
+            snprintf(msg, sizeof(msg), "inputs[%d] + count overflows the address space", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    for (int i = 0; i < m; i++)
+        if (nb > UINTPTR_MAX - reinterpret_cast<uintptr_t>(outs[i])) {
+            snprintf(msg, sizeof(msg), "outs[%d] + count overflows the address space", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    for (int i = 0; i < m; i++) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(outs[i]), hi = lo + nb;
+        for (int j = 0; j < i; j++) {
+            const uintptr_t l2 = reinterpret_cast<uintptr_t>(outs[j]);
+            if (lo < l2 + nb && l2 < hi) {
+                snprintf(msg, sizeof(msg), "outs[%d] and outs[%d] overlap", j, i);
+                return fail(MI_E_INVALID, msg);
+            }
+        }
+        for (int j = 0; j < k; j++) {
+            const uintptr_t l2 = reinterpret_cast<uintptr_t>(inputs[j]);
+            if (l2 != lo && lo < l2 + nb && l2 < hi) {
+                snprintf(msg, sizeof(msg), "outs[%d] overlaps inputs[%d] without being equal to it", i, j);
+                return fail(MI_E_INVALID, msg);
+            }
+        }
+    }
+    return 0;
+}
+
+int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt, int op,
+                        unsigned flags, hipStream_t stream) {
+    const size_t es = dtype_size(dt);
+    if (!es) return fail(MI_E_INVALID, "unknown datatype");
+    if (op < MI_OP_SUM || op > MI_OP_MAX) return fail(MI_E_INVALID, "unsupported reduction (device path: sum/prod/min/max)");
+    if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count k out of range [1,16]");
+    if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
+    if (!inputs) return fail(MI_E_INVALID, "null input list");
+    if (!outs) return fail(MI_E_INVALID, "null output list");
+    if (int rc = check_bcast_args(inputs, k, outs, m, count, es)) return rc;
+    if (count == 0) return 0;
+    // one output: mi_reduce_multi, its kernels and launch plans
+    if (m == 1) return launch_reduce(inputs, k, outs[0], count, dt, op, flags, stream);
+
+    for (int i = 0; i < k; i++)
+        if (int rc = require_gpu_visible(inputs[i], count * es)) return rc;
+    for (int i = 0; i < m; i++)
+        if (int rc = require_gpu_visible(outs[i], count * es)) return rc;
+
+    const unsigned v = canon_flags(dt, op, flags, k);
+    const Kern kern = pick(dt, op, v);
+    if (!kern.bcast) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
+
+    // The vector grid is the outputs' 16-byte grid, so they must share one
+    // misalignment; the inputs as in launch_reduce.
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(outs[0]) & 15u;
+    bool elem = (mis % es) == 0;
+    bool same_out = true, same_in = true;
+    for (int i = 1; i < m; i++) same_out = same_out && (reinterpret_cast<uintptr_t>(outs[i]) & 15u) == mis;
+    for (int i = 0; i < k; i++) {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(inputs[i]);
+        elem = elem && (p % es) == 0;
+        same_in = same_in && (p & 15u) == mis;
+    }
+    const bool vec = same_out && ((elem && same_in) || (elem && unaligned_vectors()));
+    const size_t n_per_vec = 16 / es;
+    const size_t head = vec && mis ? std::min<size_t>((16 - mis) / es, count) : 0;
+
+    BCArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < k; i++) a.in[i] = inputs[i];
+    for (int i = 0; i < m; i++) a.out[i] = outs[i];
+    a.k = k;
+    a.m = m;
+    a.count = count;
+    a.trunc_from = (count / 16) * 16;
+    a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
+    if (vec) {
+        a.head = head;
+        a.nvec = (count - head) / n_per_vec;
+        a.tail = count - head - a.nvec * n_per_vec;
+    } else {
+        a.scalar_only = 1;
+    }
+    const int cap = max_blocks();
+    hipError_t e;
+    if (vec && cap == 0 && a.nvec / kBcastBlock < 0x7FFFFFFFull) {
+        e = kern.bcast(0, stream, a, wave_cap_lds(stream, bcast_planned_waves(k, m)));
+    } else {
+        uint64_t blocks;
+        if (vec) {
+            blocks = (a.nvec + kBlock - 1) / kBlock;
+            if (cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
+        } else {
+            blocks = std::min<uint64_t>((count + kBlock - 1) / kBlock, 8192);
+        }
+        blocks = std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull);  // the stride covers the rest
+        e = kern.bcast((unsigned)blocks, stream, a, 0);
     }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return 0;
@@ -1895,6 +2070,11 @@ int mi_reduce_multi(const void* const* inputs, int k, void* out, size_t count, i
     return launch_reduce(inputs, k, out, count, dtype, op, flags, (hipStream_t)stream);
 }
 
+int mi_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dtype, int op,
+                    unsigned flags, void* stream) {
+    return launch_reduce_bcast(inputs, k, outs, m, count, dtype, op, flags, (hipStream_t)stream);
+}
+
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op, unsigned flags,
                     void* stream) {
     return guarded([&]() -> int { return launch_reduce_batch(descs, n, dtype, op, flags, (hipStream_t)stream); });
@@ -2706,7 +2886,7 @@ size_t mi_dtype_size(int dtype) { return dtype_size(dtype); }
 
 const char* mi_last_error(void) { return g_last_error.c_str(); }
 
-int mi_version(void) { return 100; }  // 0.1.0
+int mi_version(void) { return 101; }  // 0.1.1
 
 int mi_helper_cpu_count(void) { return g_helper_cpus.use ? CPU_COUNT(&g_helper_cpus.mask) : 0; }
 
@@ -2789,6 +2969,10 @@ int mi_set_residency(int k, int waves_per_cu) {
     if (waves_per_cu < 0 || waves_per_cu > 32) return fail(MI_E_INVALID, "waves_per_cu must be 0..32");
     g_residency_override[k].store(waves_per_cu, std::memory_order_relaxed);
     return 0;
+}
+
+int mi_set_bcast_store(int sc1) {
+    return g_bcast_store.exchange(sc1 ? 1 : 0, std::memory_order_relaxed);
 }
 
 int mi_set_max_blocks(int mb) {

@@ -7,6 +7,8 @@
 //   src/comp/comp.cpp:202-249    ccl_comp_batch_reduce (K-input fan-in,
 //                                optional fp32 keep-precision accumulate)
 //   src/kernels/kernels.cl:219-421  device in-place / out-of-place / fan-in
+//   src/kernels/kernels.cl:190-217, 424-560  allreduce into two buffers; the
+//                                fan-in's result written to every peer
 //
 // Design: the op is a pure HBM stream with zero data reuse,
 // so there is no LDS and no MFMA.  Every lane moves 16-byte vectors
@@ -954,6 +956,190 @@ __global__ __launch_bounds__(B) void reduce2b_kernel(R2Args a) {
                                                                                  kAuxNT);
                                 }),
         tile_rsrc(a.out, byte0, bytes), off, 0, kAuxNT);
+}
+
+// ---------------------------------------------------------------------------
+// Fold K inputs once, write the result to M outputs (mi_reduce_bcast): the
+// step that completes an allreduce on the GPU.  The reference does it as
+// allreduce_kernel_* (out = peer_out = op(in, peer_in),
+// src/kernels/kernels.cl:190-217) and as reduce_monolithic_kernel_N followed
+// by write_monolithic_kernel_N (kernels.cl:269-421, 424-560).  The fold is
+// fan_kernel's, bit for bit; the vector grid is the outputs' common 16-byte
+// grid.  An output may be exactly one of the inputs (in place): such an input
+// has the outputs' misalignment, so a lane loads exactly the bytes it later
+// stores, and every lane has all k loads back (the refold keeps them in
+// registers: no re-load) before its first store.
+// ---------------------------------------------------------------------------
+struct BCArgs {
+    const void* in[kMaxInputs];  // in[0] = accumulator start
+    void* out[kMaxInputs];       // m destinations, all at one misalignment on the vector path
+    uint64_t nvec;        // 16-byte vectors in the aligned body
+    uint64_t head;        // leading scalar elements (the outputs' misalignment)
+    uint64_t tail;        // trailing scalar elements
+    uint64_t count;       // total elements
+    uint64_t trunc_from;  // V_TAIL_TRUNC threshold (element index)
+    int k;                // inputs
+    int m;                // outputs
+    int scalar_only;      // outputs misaligned differently / operands not element-aligned: element loop
+    int store_sc1;        // stores sc1 + nt instead of nt (tuning knob, mi_set_bcast_store)
+};
+
+// k = 1 in storage precision folds nothing: mi_reduce_multi copies the bytes,
+// so the fan-out does too (a rounding step would quiet a signalling fp16 NaN).
+template <typename Tag, unsigned V>
+constexpr bool bcast_copies_k1() {
+    return Tr<Tag>::lp && !(V & V_ACC_FP32);
+}
+
+template <typename Tag, int OP, unsigned V>
+__device__ __forceinline__ void bcast_elem(const BCArgs& a, int k, int m, uint64_t idx) {
+    using S = typename Tr<Tag>::S;
+    using C = typename Tr<Tag>::C;
+    const S s0 = static_cast<const S*>(a.in[0])[idx];
+    C acc = widen<Tag>(s0);
+    for (int i = 1; i < k; i++) acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(a.in[i])[idx]), acc);
+    S r = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, a.trunc_from), s0);
+    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? s0 : r;
+    for (int o = 0; o < m; o++) static_cast<S*>(a.out[o])[idx] = r;
+}
+
+// Shared tail of the two kernels below: the m stores of a lane's result, a
+// wave-uniform loop over the output pointers (one descriptor per iteration,
+// read from the kernel arguments by a uniform index: no per-lane array).
+__device__ __forceinline__ void bcast_store(const BCArgs& a, int m, u32x4 r, uint64_t byte0, uint32_t bytes,
+                                            uint32_t off) {
+    if (a.store_sc1) {
+#pragma nounroll
+        for (int o = 0; o < m; o++)
+            __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out[o], byte0, bytes), off, 0, kAuxSC1NT);
+    } else {
+#pragma nounroll
+        for (int o = 0; o < m; o++)
+            __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out[o], byte0, bytes), off, 0, kAuxNT);
+    }
+}
+
+// One tile of B vectors per block, every stream through one buffer descriptor
+// per tile (range = the tile's valid bytes: lanes past the end load zeros and
+// their stores are dropped, no guard branches).  All k loads are issued before
+// the first combine, then fan_kernel's fold, then the m stores.
+template <typename Tag, int OP, unsigned V, int B, int KMAX>
+__global__ __launch_bounds__(B) void bcast_kernel(BCArgs a) {
+    using S = typename Tr<Tag>::S;
+    constexpr int N = 16 / sizeof(S);
+    const int k = a.k, m = a.m;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < a.head) bcast_elem<Tag, OP, V>(a, k, m, threadIdx.x);
+        if (threadIdx.x < a.tail) bcast_elem<Tag, OP, V>(a, k, m, a.head + a.nvec * N + threadIdx.x);
+    }
+    const uint64_t t0 = (uint64_t)blockIdx.x * B;
+    if (t0 >= a.nvec) return;
+    const uint64_t left = a.nvec - t0;
+    const uint32_t bytes = (uint32_t)(left < (uint64_t)B ? left : (uint64_t)B) * 16u;
+    const uint64_t byte0 = a.head * sizeof(S) + t0 * 16;
+    const uint32_t off = threadIdx.x * 16u;
+    // every input pointer before the first branch, as in fan_kernel
+    const void* in[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+        in[i] = a.in[i];
+        asm volatile("" ::"s"(in[i]));
+    }
+    u32x4 x[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; i++)
+        if (i < k) x[i] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(in[i], byte0, bytes), off, 0, kAuxNT);
+    u32x4 r;
+    if constexpr (packed_int<Tag>()) {
+        r = x[0];
+#pragma unroll
+        for (int i = 1; i < KMAX; i++)
+            if (i < k) r = pk_op4<Tag, OP>(x[i], r);
+    } else {
+        // written out, not through fold_vec: see fan_kernel on scratch
+        using C = typename Tr<Tag>::C;
+        C acc[N];
+        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x[0]);
+#pragma unroll
+        for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
+#pragma unroll
+        for (int i = 1; i < KMAX; i++) {
+            if (i < k) {
+                const Pack<S> pi = __builtin_bit_cast(Pack<S>, x[i]);
+#pragma unroll
+                for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V, false>(widen<Tag>(pi.e[e]), acc[e]);
+            }
+        }
+        Pack<S> pr;
+        const uint64_t e0 = a.head + (t0 + threadIdx.x) * N;
+#pragma unroll
+        for (int e = 0; e < N; e++) pr.e[e] = finish_fold<Tag, V, false>(acc[e], e0 + e, a.trunc_from);
+        r = x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, a.trunc_from);
+        if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x[0] : r;
+    }
+    bcast_store(a, m, r, byte0, bytes, off);
+}
+
+// The grid-stride form, for launches under mi_set_max_blocks and for the
+// element loop (`scalar_only`: outputs at differing misalignments, or operands
+// off the vector path).  The blocks stride over tiles of B vectors addressed
+// as above; the fold is reduce_kernel's (a runtime loop over the inputs, the
+// next input's load in flight while one is combined, every step with the x86
+// NaN bits), so a lane still has all k loads back before its first store.
+// Same bits as bcast_kernel.
+template <typename Tag, int OP, unsigned V, int B>
+__global__ __launch_bounds__(B) void bcast_stride_kernel(BCArgs a) {
+    using S = typename Tr<Tag>::S;
+    constexpr int N = 16 / sizeof(S);
+    const int k = a.k, m = a.m;
+    if (a.scalar_only) {
+        for (uint64_t i = (uint64_t)blockIdx.x * B + threadIdx.x; i < a.count; i += (uint64_t)gridDim.x * B)
+            bcast_elem<Tag, OP, V>(a, k, m, i);
+        return;
+    }
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < a.head) bcast_elem<Tag, OP, V>(a, k, m, threadIdx.x);
+        if (threadIdx.x < a.tail) bcast_elem<Tag, OP, V>(a, k, m, a.head + a.nvec * N + threadIdx.x);
+    }
+    const uint32_t off = threadIdx.x * 16u;
+    for (uint64_t t0 = (uint64_t)blockIdx.x * B; t0 < a.nvec; t0 += (uint64_t)gridDim.x * B) {
+        const uint64_t left = a.nvec - t0;
+        const uint32_t bytes = (uint32_t)(left < (uint64_t)B ? left : (uint64_t)B) * 16u;
+        const uint64_t byte0 = a.head * sizeof(S) + t0 * 16;
+        const u32x4 x0 = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[0], byte0, bytes), off, 0, kAuxNT);
+        u32x4 cur = x0, r = x0;
+        if (k >= 2) cur = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[1], byte0, bytes), off, 0, kAuxNT);
+        using C = typename Tr<Tag>::C;
+        C acc[N];
+        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x0);
+        if constexpr (!packed_int<Tag>()) {
+#pragma unroll
+            for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
+        }
+        for (int i = 1; i < k; i++) {
+            u32x4 nxt = cur;
+            if (i + 1 < k)
+                nxt = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[i + 1], byte0, bytes), off, 0, kAuxNT);
+            if constexpr (packed_int<Tag>()) {
+                r = pk_op4<Tag, OP>(cur, r);
+            } else {
+                const Pack<S> pi = __builtin_bit_cast(Pack<S>, cur);
+#pragma unroll
+                for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V>(widen<Tag>(pi.e[e]), acc[e]);
+            }
+            cur = nxt;
+        }
+        if constexpr (!packed_int<Tag>()) {
+            Pack<S> pr;
+            const uint64_t e0 = a.head + (t0 + threadIdx.x) * N;
+#pragma unroll
+            for (int e = 0; e < N; e++)
+                pr.e[e] = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc[e], e0 + e, a.trunc_from), p0.e[e]);
+            r = __builtin_bit_cast(u32x4, pr);
+            if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x0 : r;
+        }
+        bcast_store(a, m, r, byte0, bytes, off);
+    }
 }
 
 // ---------------------------------------------------------------------------
