@@ -23,6 +23,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "lib"
 ARCH = os.environ.get("MI_OFFLOAD_ARCH", "gfx950")
+PROBE = ROOT / "tools" / "probe_kernels.hpp"  # kernels only the sweeps launch
 
 
 def _hipcc() -> str:
@@ -46,7 +47,7 @@ def _run(cmd: list[str]) -> None:
 
 def build_mi_reduce(force: bool = False) -> Path:
     out = LIB / "libmi_reduce.so"
-    deps = [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", ROOT / "include" / "mi_reduce.h"]
+    deps = [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", CSRC / "vec_grid.hpp", ROOT / "include" / "mi_reduce.h"]
     if force or _stale(out, deps):
         LIB.mkdir(exist_ok=True)
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
@@ -86,7 +87,7 @@ def build_shim(force: bool = False) -> Path:
 def build_sweep(force: bool = False) -> Path:
     out = ROOT / "tools" / "reduce_sweep"
     src = ROOT / "tools" / "reduce_sweep.hip"
-    deps = [src, CSRC / "reduce_kernels.hpp"]
+    deps = [src, PROBE, CSRC / "reduce_kernels.hpp"]
     if src.exists() and (force or _stale(out, deps)):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-Wall",
               "-o", str(out), str(src)])
@@ -104,7 +105,7 @@ def build_policy_sweep(force: bool = False) -> Path:
 def build_fan_sweep(force: bool = False) -> Path:
     out = ROOT / "tools" / "fan_sweep"
     src = ROOT / "tools" / "fan_sweep.hip"
-    deps = [src, CSRC / "reduce_kernels.hpp"]
+    deps = [src, PROBE, CSRC / "reduce_kernels.hpp"]
     if src.exists() and (force or _stale(out, deps)):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-Wall", "-o", str(out), str(src)])
     return out
@@ -113,7 +114,7 @@ def build_fan_sweep(force: bool = False) -> Path:
 def build_burst_sweep(force: bool = False) -> Path:
     out = ROOT / "tools" / "burst_sweep"
     src = ROOT / "tools" / "burst_sweep.hip"
-    if src.exists() and (force or _stale(out, [src, CSRC / "reduce_kernels.hpp"])):
+    if src.exists() and (force or _stale(out, [src, PROBE, CSRC / "reduce_kernels.hpp"])):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-Wall", "-o", str(out), str(src)])
     return out
 
@@ -129,7 +130,7 @@ def build_copy_sweep(force: bool = False) -> Path:
 def build_lds_stage_sweep(force: bool = False) -> Path:
     out = ROOT / "tools" / "lds_stage_sweep"
     src = ROOT / "tools" / "lds_stage_sweep.hip"
-    if src.exists() and (force or _stale(out, [src, CSRC / "reduce_kernels.hpp"])):
+    if src.exists() and (force or _stale(out, [src, PROBE, CSRC / "reduce_kernels.hpp"])):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-Wall", "-o", str(out), str(src)])
     return out
 
@@ -221,7 +222,7 @@ def build_asan(force: bool = False) -> Path:
     adir.mkdir(parents=True, exist_ok=True)
     san = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fno-omit-frame-pointer"]
     mi = adir / "libmi_reduce.so"
-    if force or _stale(mi, [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp"]):
+    if force or _stale(mi, [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", CSRC / "vec_grid.hpp"]):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", *san,
               "-o", str(mi), str(CSRC / "mi_reduce.hip")])
     shim = adir / "libccl_comp_hip.so"

@@ -2,7 +2,11 @@
 //
 // Host half of the MI355X-native local reduction: variant canonicalisation,
 // kernel selection, launch geometry, per-thread streams and the
-// host-operand staging pipeline.  Kernels: reduce_kernels.hpp.
+// host-operand staging pipeline.  Kernels: reduce_kernels.hpp; the
+// head / body / tail split of a launch: vec_grid.hpp.  Shared by the entry
+// points, one definition each: Knob (lazy environment knobs), DeviceScope
+// (switch device, restore on every path), check_* (argument refusals and
+// their messages), stride_grid (grid of the grid-stride fallbacks).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +30,7 @@
 
 #include "../../include/mi_reduce.h"
 #include "reduce_kernels.hpp"
+#include "vec_grid.hpp"
 
 using namespace mi;
 
@@ -56,20 +61,37 @@ int hip_fail(hipError_t e, const char* what) {
 constexpr int kUnroll = 4;  // 16-byte vectors per lane per input per tile
 constexpr int kMem = 3;     // non-temporal loads and stores (sweep: profiles/round1_sweep.jsonl)
 
-std::atomic<int> g_max_blocks{-1};  // -1 = not yet read from env; 0 = no cap
-std::atomic<int> g_host_mode{-1};   // -1 = not yet read from env
-
-std::atomic<int> g_sync_mode{-1};  // -1 = not yet read from env
-
-int sync_mode() {
-    int v = g_sync_mode.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* s = getenv("MI_REDUCE_SYNC");
-        v = (s && strcmp(s, "spin") == 0) ? MI_SYNC_SPIN : MI_SYNC_BLOCK;
-        g_sync_mode.store(v, std::memory_order_relaxed);
+// A knob is read from its environment variable (`parse` gets getenv's result,
+// null when unset) the first time it is asked for; mi_set_* stores over it.
+struct Knob {
+    const char* env;
+    int (*parse)(const char*);
+    std::atomic<int> v{-1};  // -1 = not yet read from env
+    int get() {
+        int x = v.load(std::memory_order_relaxed);
+        if (x < 0) {
+            x = parse(getenv(env));
+            v.store(x, std::memory_order_relaxed);
+        }
+        return x;
     }
-    return v;
-}
+    void set(int x) { v.store(x, std::memory_order_relaxed); }
+};
+
+Knob g_sync_mode{"MI_REDUCE_SYNC",
+                 [](const char* s) { return (s && strcmp(s, "spin") == 0) ? (int)MI_SYNC_SPIN : (int)MI_SYNC_BLOCK; }};
+Knob g_host_mode{"MI_REDUCE_HOST_MODE",
+                 [](const char* s) { return (s && strcmp(s, "staged") == 0) ? (int)MI_HOST_STAGED : (int)MI_HOST_AUTO; }};
+// Operands whose misalignments differ take the vector kernels (1, default)
+// or the element loop (0).  Env MI_REDUCE_UNALIGNED=0 selects the loop.
+Knob g_unaligned{"MI_REDUCE_UNALIGNED", [](const char* s) { return (s && strcmp(s, "0") == 0) ? 0 : 1; }};
+// grid cap of the grid-stride kernels; 0 = no cap
+Knob g_max_blocks{"MI_REDUCE_MAX_BLOCKS", [](const char* s) { return s ? std::max(0, atoi(s)) : 0; }};
+
+int sync_mode() { return g_sync_mode.get(); }
+int host_mode() { return g_host_mode.get(); }
+int unaligned_vectors() { return g_unaligned.get(); }
+int max_blocks() { return g_max_blocks.get(); }
 
 // Wait for a stream: spin on hipStreamQuery (lowest latency for the
 // synchronous src/comp contract) or the runtime's blocking wait.
@@ -82,39 +104,21 @@ hipError_t wait_stream(hipStream_t s) {
     }
 }
 
-int host_mode() {
-    int v = g_host_mode.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* s = getenv("MI_REDUCE_HOST_MODE");
-        v = (s && strcmp(s, "staged") == 0) ? MI_HOST_STAGED : MI_HOST_AUTO;
-        g_host_mode.store(v, std::memory_order_relaxed);
+// Makes `device` the calling thread's current device until the scope ends:
+// the previous one comes back on every path out.
+struct DeviceScope {
+    int prev = -1, cur = -1;
+    int enter(int device, const char* set_what = "hipSetDevice(d->device)") {
+        hipError_t e = hipGetDevice(&prev);
+        if (e != hipSuccess) return hip_fail(e, "hipGetDevice(&prev)");
+        if (prev != device && (e = hipSetDevice(device)) != hipSuccess) return hip_fail(e, set_what);
+        cur = device;
+        return 0;
     }
-    return v;
-}
-
-// Operands whose misalignments differ take the vector kernels (1, default)
-// or the element loop (0).  Env MI_REDUCE_UNALIGNED=0 selects the loop.
-std::atomic<int> g_unaligned{-1};  // -1 = not yet read from env
-
-int unaligned_vectors() {
-    int v = g_unaligned.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* s = getenv("MI_REDUCE_UNALIGNED");
-        v = (s && strcmp(s, "0") == 0) ? 0 : 1;
-        g_unaligned.store(v, std::memory_order_relaxed);
+    ~DeviceScope() {
+        if (cur >= 0 && prev != cur) (void)hipSetDevice(prev);
     }
-    return v;
-}
-
-int max_blocks() {
-    int v = g_max_blocks.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* s = getenv("MI_REDUCE_MAX_BLOCKS");
-        v = s ? std::max(0, atoi(s)) : 0;
-        g_max_blocks.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
+};
 
 size_t dtype_size(int dt) {
     switch (dt) {
@@ -557,6 +561,53 @@ int require_gpu_visible(const void* p, size_t bytes = 1) {
     return 0;
 }
 
+// The argument checks the entry points share, one message each.  Where an
+// entry point's order of refusals differs, it strings the pieces together
+// itself.
+int check_dtype(int dt, size_t* es) {
+    *es = dtype_size(dt);
+    return *es ? 0 : fail(MI_E_INVALID, "unknown datatype");
+}
+int check_op(int op) {
+    if (op < MI_OP_SUM || op > MI_OP_MAX) return fail(MI_E_INVALID, "unsupported reduction (device path: sum/prod/min/max)");
+    return 0;
+}
+int check_k(int k) {
+    return (k < 1 || k > MI_MAX_INPUTS) ? fail(MI_E_INVALID, "input count out of range [1,16]") : 0;
+}
+int check_operands(const void* const* inputs, int k, const void* out) {
+    if (!out) return fail(MI_E_INVALID, "null output");
+    for (int i = 0; i < k; i++)
+        if (!inputs[i]) return fail(MI_E_INVALID, "null input");
+    return 0;
+}
+// A fold's arguments: dtype (*es = its size), op (null: the caller's launch
+// checks it), k, and, unless count is 0 (nothing to do: the caller returns 0),
+// the operands.
+int check_fold_args(int dt, const int* op, int k, size_t count, const void* const* inputs, const void* out,
+                    size_t* es) {
+    if (int rc = check_dtype(dt, es)) return rc;
+    if (op)
+        if (int rc = check_op(*op)) return rc;
+    if (int rc = check_k(k)) return rc;
+    return count ? check_operands(inputs, k, out) : 0;
+}
+
+// Grid of a grid-stride fallback (a launch under mi_set_max_blocks, a body
+// too large for one tile per block, or the element loop): one block per tile
+// of `tile` vectors up to the cap, or the element loop's blocks of kBlock
+// elements, at most 8192; the stride covers what the grid does not.
+unsigned stride_grid(const VecGrid& g, uint64_t tile, size_t count, int cap) {
+    uint64_t blocks;
+    if (g.vec) {
+        blocks = (g.nvec + tile - 1) / tile;
+        if (cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
+    } else {
+        blocks = std::min<uint64_t>((count + kBlock - 1) / kBlock, 8192);
+    }
+    return (unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull);
+}
+
 // ---------------------------------------------------------------------------
 // the asynchronous core: out = fold(inputs[0..k-1]) on device pointers
 // ---------------------------------------------------------------------------
@@ -565,14 +616,9 @@ int require_gpu_visible(const void* p, size_t bytes = 1) {
 // staging and bounce buffers), so they are not looked up again.
 int launch_reduce(const void* const* inputs, int k, void* out, size_t count, int dt, int op,
                   unsigned flags, hipStream_t stream, bool visible = false) {
-    const size_t es = dtype_size(dt);
-    if (!es) return fail(MI_E_INVALID, "unknown datatype");
-    if (op < MI_OP_SUM || op > MI_OP_MAX) return fail(MI_E_INVALID, "unsupported reduction (device path: sum/prod/min/max)");
-    if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count out of range [1,16]");
+    size_t es;
+    if (int rc = check_fold_args(dt, &op, k, count, inputs, out, &es)) return rc;
     if (count == 0) return 0;
-    if (!out) return fail(MI_E_INVALID, "null output");
-    for (int i = 0; i < k; i++)
-        if (!inputs[i]) return fail(MI_E_INVALID, "null input");
 
     if (!visible) {
         for (int i = 0; i < k; i++)
@@ -590,43 +636,26 @@ int launch_reduce(const void* const* inputs, int k, void* out, size_t count, int
     // VCVTNEPS2BF16 main part / scalar tail split of ccl_convert_fp32_to_bf16_arrays
     const uint64_t trunc_from = (count / 16) * 16;
 
-    // The vector grid is the output's 16-byte grid: a scalar head up to the
-    // first 16-byte boundary of `out`, a vector body, a scalar tail.  Inputs
-    // need only be aligned to their element size: gfx950 serves a 16-byte
-    // load from any byte address (profiles/round1_unaligned_probe.jsonl: right
-    // bytes at every offset; 98-99 % of the aligned stream rate at 4-byte
-    // offsets, 89 % at 1- and 2-byte offsets), so ring chunks at arbitrary
-    // element offsets still stream as 16-byte vectors.  Operands that are not
-    // aligned to their element size take the element loop (general kernel).
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(out) & 15u;
-    bool elem = (mis % es) == 0;
-    bool same = elem;
-    for (int i = 0; i < k; i++) {
-        const uintptr_t p = reinterpret_cast<uintptr_t>(inputs[i]);
-        elem = elem && (p % es) == 0;
-        same = same && (p & 15u) == mis;
-    }
-    const bool vec = same || (elem && unaligned_vectors());
-    const size_t n_per_vec = 16 / es;
-    const size_t head = vec && mis ? std::min<size_t>((16 - mis) / es, count) : 0;
-    const uint64_t nvec = vec ? (count - head) / n_per_vec : 0;
-    const size_t tail = vec ? count - head - nvec * n_per_vec : 0;
+    // The output's 16-byte grid (vec_grid.hpp); without one, the element loop
+    // of the general kernel.
+    const void* const out1 = out;
+    const VecGrid g = plan_vec_grid(es, count, &out1, 1, inputs, k, unaligned_vectors() != 0);
 
     // A grid cap (tuning / test knob) routes everything through the
     // grid-stride general kernel; otherwise one tile per block.
     const int cap = max_blocks();
     hipError_t e;
-    if (vec && cap == 0 && k == 2) {
+    if (g.vec && cap == 0 && k == 2) {
         R2Args r;
         r.acc = inputs[0];
         r.in = inputs[1];
         r.out = out;
-        r.nvec = nvec;
-        r.head = (uint32_t)head;
-        r.tail = (uint32_t)tail;
+        r.nvec = g.nvec;
+        r.head = (uint32_t)g.head;
+        r.tail = (uint32_t)g.tail;
         r.trunc_from = trunc_from;
         const uint64_t tile = (uint64_t)kB2 * kU2;
-        uint64_t blocks = std::max<uint64_t>((nvec + tile - 1) / tile, 1);
+        uint64_t blocks = std::max<uint64_t>((g.nvec + tile - 1) / tile, 1);
         if (blocks > 0x7FFFFFFFull) return fail(MI_E_UNSUPPORTED, "bucket too large for one launch");
         e = kern.lean(dim3((unsigned)blocks), stream, r, wave_cap_lds(stream, planned_waves(2)));
     } else {
@@ -637,29 +666,15 @@ int launch_reduce(const void* const* inputs, int k, void* out, size_t count, int
         a.k = k;
         a.count = count;
         a.trunc_from = trunc_from;
-        if (vec) {
-            a.head = head;
-            a.nvec = nvec;
-            a.tail = tail;
-        } else {
-            a.scalar_only = 1;
-        }
+        a.head = g.head;
+        a.nvec = g.nvec;
+        a.tail = g.tail;
+        a.scalar_only = !g.vec;
         // fan tiles are 64 vectors: one launch covers 2^37 vectors (2 TiB)
-        if (vec && cap == 0 && nvec / kFanBlock < 0x7FFFFFFFull) {
+        if (g.vec && cap == 0 && g.nvec / kFanBlock < 0x7FFFFFFFull)
             e = kern.fan(stream, a, wave_cap_lds(stream, planned_waves(k)));
-        } else {
-            uint64_t blocks;
-            if (vec) {
-                const uint64_t tile = (uint64_t)kBlock * kUnroll;
-                blocks = (a.nvec + tile - 1) / tile;
-                if (cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
-                if (blocks == 0) blocks = 1;
-            } else {
-                blocks = std::min<uint64_t>((count + kBlock - 1) / kBlock, 8192);
-            }
-            if (blocks > 0x7FFFFFFFull) blocks = 0x7FFFFFFFull;  // grid-stride covers the rest
-            e = kern.general(dim3((unsigned)blocks), stream, a);
-        }
+        else
+            e = kern.general(dim3(stride_grid(g, (uint64_t)kBlock * kUnroll, count, cap)), stream, a);
     }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return 0;
@@ -742,9 +757,9 @@ int check_bcast_args(const void* const* inputs, int k, void* const* outs, int m,
 
 int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt, int op,
                         unsigned flags, hipStream_t stream) {
-    const size_t es = dtype_size(dt);
-    if (!es) return fail(MI_E_INVALID, "unknown datatype");
-    if (op < MI_OP_SUM || op > MI_OP_MAX) return fail(MI_E_INVALID, "unsupported reduction (device path: sum/prod/min/max)");
+    size_t es;
+    if (int rc = check_dtype(dt, &es)) return rc;
+    if (int rc = check_op(op)) return rc;
     if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count k out of range [1,16]");
     if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
     if (!inputs) return fail(MI_E_INVALID, "null input list");
@@ -763,20 +778,8 @@ int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int
     const Kern kern = pick(dt, op, v);
     if (!kern.bcast) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
 
-    // The vector grid is the outputs' 16-byte grid, so they must share one
-    // misalignment; the inputs as in launch_reduce.
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(outs[0]) & 15u;
-    bool elem = (mis % es) == 0;
-    bool same_out = true, same_in = true;
-    for (int i = 1; i < m; i++) same_out = same_out && (reinterpret_cast<uintptr_t>(outs[i]) & 15u) == mis;
-    for (int i = 0; i < k; i++) {
-        const uintptr_t p = reinterpret_cast<uintptr_t>(inputs[i]);
-        elem = elem && (p % es) == 0;
-        same_in = same_in && (p & 15u) == mis;
-    }
-    const bool vec = same_out && ((elem && same_in) || (elem && unaligned_vectors()));
-    const size_t n_per_vec = 16 / es;
-    const size_t head = vec && mis ? std::min<size_t>((16 - mis) / es, count) : 0;
+    // the outputs' common 16-byte grid (vec_grid.hpp)
+    const VecGrid g = plan_vec_grid(es, count, outs, m, inputs, k, unaligned_vectors() != 0);
 
     BCArgs a;
     memset(&a, 0, sizeof(a));
@@ -787,28 +790,16 @@ int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int
     a.count = count;
     a.trunc_from = (count / 16) * 16;
     a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
-    if (vec) {
-        a.head = head;
-        a.nvec = (count - head) / n_per_vec;
-        a.tail = count - head - a.nvec * n_per_vec;
-    } else {
-        a.scalar_only = 1;
-    }
+    a.head = g.head;
+    a.nvec = g.nvec;
+    a.tail = g.tail;
+    a.scalar_only = !g.vec;
     const int cap = max_blocks();
     hipError_t e;
-    if (vec && cap == 0 && a.nvec / kBcastBlock < 0x7FFFFFFFull) {
+    if (g.vec && cap == 0 && g.nvec / kBcastBlock < 0x7FFFFFFFull)
         e = kern.bcast(0, stream, a, wave_cap_lds(stream, bcast_planned_waves(k, m)));
-    } else {
-        uint64_t blocks;
-        if (vec) {
-            blocks = (a.nvec + kBlock - 1) / kBlock;
-            if (cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
-        } else {
-            blocks = std::min<uint64_t>((count + kBlock - 1) / kBlock, 8192);
-        }
-        blocks = std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull);  // the stride covers the rest
-        e = kern.bcast((unsigned)blocks, stream, a, 0);
-    }
+    else
+        e = kern.bcast(stride_grid(g, kBlock, count, cap), stream, a, 0);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return 0;
 }
@@ -856,9 +847,9 @@ int check_batch_disjoint(const mi_reduce_desc_t* d, int n, size_t es) {
 
 int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsigned flags,
                         hipStream_t stream) {
-    const size_t es = dtype_size(dt);
-    if (!es) return fail(MI_E_INVALID, "unknown datatype");
-    if (op < MI_OP_SUM || op > MI_OP_MAX) return fail(MI_E_INVALID, "unsupported reduction (device path: sum/prod/min/max)");
+    size_t es;
+    if (int rc = check_dtype(dt, &es)) return rc;
+    if (int rc = check_op(op)) return rc;
     if (n < 0) return fail(MI_E_INVALID, "negative descriptor count");
     if (n == 0) return 0;
     if (!d) return fail(MI_E_INVALID, "null descriptor list");
@@ -874,7 +865,6 @@ int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsign
     if (!kern.batch) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
 
     const uint64_t tile = (uint64_t)kB2 * kU2;
-    const size_t n_per_vec = 16 / es;
     BArgs a;
     memset(&a, 0, sizeof(a));
     uint64_t blocks = 0;
@@ -890,16 +880,10 @@ int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsign
     for (int i = 0; i < n; i++) {
         const size_t count = d[i].count;
         if (!count) continue;
-        // the same vector-grid decision as launch_reduce for k = 2
-        const uintptr_t mis = reinterpret_cast<uintptr_t>(d[i].inout) & 15u;
-        const uintptr_t pin = reinterpret_cast<uintptr_t>(d[i].in);
-        const bool elem = (mis % es) == 0 && (pin % es) == 0;
-        const bool vec = (elem && (pin & 15u) == mis) || (elem && unaligned_vectors());
-        const uint64_t head = vec && mis ? std::min<size_t>((16 - mis) / es, count) : 0;
-        const uint64_t nvec = vec ? (count - head) / n_per_vec : 0;
-        const uint64_t nb = std::max<uint64_t>((nvec + tile - 1) / tile, 1);
-        if (!vec || max_blocks() != 0 || nb > 0x40000000ull) {  // element loop / grid knob / huge: own launch
-            const void* ins[2] = {d[i].inout, d[i].in};
+        const void* const ins[2] = {d[i].inout, d[i].in};
+        const VecGrid g = plan_vec_grid(es, count, ins, 1, ins + 1, 1, unaligned_vectors() != 0);
+        const uint64_t nb = std::max<uint64_t>((g.nvec + tile - 1) / tile, 1);
+        if (!g.vec || max_blocks() != 0 || nb > 0x40000000ull) {  // element loop / grid knob / huge: own launch
             if (int rc = launch_reduce(ins, 2, d[i].inout, count, dt, op, flags, stream)) return rc;
             continue;
         }
@@ -909,9 +893,9 @@ int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsign
         a.acc[j] = d[i].inout;
         a.in[j] = d[i].in;
         a.out[j] = d[i].inout;
-        a.nvec[j] = nvec;
-        a.head[j] = (uint8_t)head;
-        a.tail[j] = (uint8_t)(count - head - nvec * n_per_vec);
+        a.nvec[j] = g.nvec;
+        a.head[j] = (uint8_t)g.head;
+        a.tail[j] = (uint8_t)g.tail;
         a.trunc_from[j] = (count / 16) * 16;
         a.block0[j] = (uint32_t)blocks;
         blocks += nb;
@@ -1367,13 +1351,8 @@ int get_ctx(int device, DevCtx** out) {
         // half-made context (a null stream would be the legacy default
         // stream) cached for the thread, and the caller's device is restored
         // on every path.
-        int prev = 0;
-        MI_HIP(hipGetDevice(&prev));
-        struct Restore {
-            int dev;
-            ~Restore() { (void)hipSetDevice(dev); }
-        } restore{prev};
-        MI_HIP(hipSetDevice(device));
+        DeviceScope scope;
+        if (int rc = scope.enter(device, "hipSetDevice(device)")) return rc;
         ensure_exit_hook();
         std::unique_ptr<DevCtx> d(new DevCtx());
         d->device = device;
@@ -1463,13 +1442,9 @@ int reduce_issue(const void* const* inputs, int k, void* out, size_t count, int 
                  const Kinds* pre = nullptr) {
     *ctx = nullptr;
     *used = 0;
-    const size_t es = dtype_size(dt);
-    if (!es) return fail(MI_E_INVALID, "unknown datatype");
-    if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count out of range [1,16]");
+    size_t es;
+    if (int rc = check_fold_args(dt, nullptr, k, count, inputs, out, &es)) return rc;
     if (count == 0) return 0;
-    if (!out) return fail(MI_E_INVALID, "null output");
-    for (int i = 0; i < k; i++)
-        if (!inputs[i]) return fail(MI_E_INVALID, "null input");
 
     Kinds own;
     if (!pre || !pre->valid) {
@@ -1505,15 +1480,8 @@ int reduce_issue(const void* const* inputs, int k, void* out, size_t count, int 
     int rc = get_ctx(device, &d);
     if (rc) return rc;
     *ctx = d;
-    int prev = 0;
-    MI_HIP(hipGetDevice(&prev));
-    if (prev != d->device) MI_HIP(hipSetDevice(d->device));
-    struct Restore {
-        int dev, cur;
-        ~Restore() {
-            if (dev != cur) (void)hipSetDevice(dev);
-        }
-    } restore{prev, d->device};
+    DeviceScope scope;
+    if ((rc = scope.enter(d->device))) return rc;
 
     // zero-copy: pinned host operands are read/written by the kernel in place
     // over PCIe (both directions at once); device operands as they are
@@ -2020,7 +1988,7 @@ int launch_convert(const void* src, int sdt, void* dst, int ddt, size_t count, u
     const bool same = (sa & 15u) == 0 && (da & 15u) == 0;
     const bool vec = (sa % ss) == 0 && (da % ds) == 0 && (same || unaligned_vectors());
     a.scalar_only = vec ? 0 : 1;
-    a.head = vec ? std::min<uint64_t>(((16 - (da & 15u)) & 15u) / ds, count) : 0;
+    a.head = vec ? grid_head(da, ds, count) : 0;
     a.ngroups = vec ? (count - a.head) / 8 : 0;
     const uint64_t work = a.scalar_only ? count : std::max<uint64_t>(a.ngroups, 1);
     uint64_t blocks = std::min<uint64_t>((work + kConvBlock - 1) / kConvBlock, 1u << 20);
@@ -2175,15 +2143,8 @@ int mi_convert_sync(const void* src, int src_dtype, void* dst, int dst_dtype, si
         DevCtx* d = nullptr;
         int rc = get_ctx(device, &d);
         if (rc) return rc;
-        int prev = 0;
-        MI_HIP(hipGetDevice(&prev));
-        if (prev != d->device) MI_HIP(hipSetDevice(d->device));
-        struct Restore {
-            int dev, cur;
-            ~Restore() {
-                if (dev != cur) (void)hipSetDevice(dev);
-            }
-        } restore{prev, d->device};
+        DeviceScope scope;
+        if ((rc = scope.enter(d->device))) return rc;
         const uint64_t trunc_from = (count / 16) * 16;
         if (ks == PK_DEVICE && kd == PK_DEVICE) {
             rc = launch_convert(src, src_dtype, dst, dst_dtype, count, flags, d->stream[0], trunc_from);
@@ -2260,19 +2221,15 @@ int reduce_start(const void* const* inputs, int k, void* out, size_t count, int 
         *req = nullptr;
         if (!inputs) return fail(MI_E_INVALID, "null input list");
         t_async_issued = true;
-        if (!dtype_size(dtype)) return fail(MI_E_INVALID, "unknown datatype");
-        if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count out of range [1,16]");
+        size_t es;
+        if (int rc = check_fold_args(dtype, nullptr, k, count, inputs, out, &es)) return rc;
         if (count > 0) {
-            if (!out) return fail(MI_E_INVALID, "null output");
-            for (int i = 0; i < k; i++)
-                if (!inputs[i]) return fail(MI_E_INVALID, "null input");
-            if (op < MI_OP_SUM || op > MI_OP_MAX)
-                return fail(MI_E_INVALID, "unsupported reduction (device path: sum/prod/min/max)");
+            if (int rc = check_op(op)) return rc;
             // Staged work runs on the calling thread's worker.  While that
             // worker still has requests of this thread, later requests go
             // there too, so a thread's requests run in submission order
             // whatever their pointer kinds.
-            if (needs_staging(inputs, k, out, count * dtype_size(dtype)) || t_stage.busy()) {
+            if (needs_staging(inputs, k, out, count * es) || t_stage.busy()) {
                 auto j = make_job(inputs, k, out, count, dtype, op, flags, device, true);
                 t_stage.submit(j);
                 mi_request* r = new mi_request();
@@ -2294,9 +2251,8 @@ int reduce_start(const void* const* inputs, int k, void* out, size_t count, int 
         r->t0 = t0;
         if (d) {
             r->device = d->device;
-            int prev = 0;
-            MI_HIP(hipGetDevice(&prev));
-            if (prev != d->device) MI_HIP(hipSetDevice(d->device));
+            DeviceScope scope;
+            rc = scope.enter(d->device);
             for (int s = 0; s < 2 && rc == 0; s++) {
                 if (!(used & (1 << s))) continue;
                 hipError_t e = hipEventCreateWithFlags(&r->ev[r->nev], t0 ? hipEventDefault : hipEventDisableTiming);
@@ -2304,7 +2260,6 @@ int reduce_start(const void* const* inputs, int k, void* out, size_t count, int 
                 if (e != hipSuccess) rc = hip_fail(e, "hipEventRecord");
                 r->nev++;
             }
-            if (prev != d->device) (void)hipSetDevice(prev);
         }
         if (rc) {
             mi_request_free(r);
@@ -2432,9 +2387,9 @@ int mi_reduce_multi_sync_sharded(const void* const* inputs, int k, void* out, si
     return guarded([&]() -> int {
         t_stage.wait_idle();  // this thread's earlier asynchronous requests come first
         if (!inputs || !devices || nshards < 1) return fail(MI_E_INVALID, "bad shard arguments");
-        if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count out of range [1,16]");
-        const size_t es = dtype_size(dtype);
-        if (!es) return fail(MI_E_INVALID, "unknown datatype");
+        if (int rc = check_k(k)) return rc;
+        size_t es;
+        if (int rc = check_dtype(dtype, &es)) return rc;
         if (nshards == 1 || count == 0) return reduce_sync(inputs, k, out, count, dtype, op, flags, devices[0]);
         // Shards start on 256-element boundaries, so the bf16 count % 16 tail
         // (MI_F_BF16_TAIL_TRUNC16) lies in the last shard exactly as in the
@@ -2485,7 +2440,9 @@ int mi_reduce_sharded(int nshards, const int* devices, const void* const* inputs
                       const size_t* counts, int dtype, int op, unsigned flags) {
     return guarded([&]() -> int {
         if (nshards < 1 || !devices || !inputs || !outs || !counts) return fail(MI_E_INVALID, "bad shard arguments");
-        if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count out of range [1,16]");
+        if (int rc = check_k(k)) return rc;
+        // one device after another, failures of the switch ignored while
+        // waiting: not DeviceScope's one-device form
         int prev = 0;
         MI_HIP(hipGetDevice(&prev));
         std::vector<DevCtx*> ctx((size_t)nshards, nullptr);
@@ -2530,7 +2487,7 @@ int mi_copy(const void* src, void* dst, size_t bytes, int nontemporal, void* str
     if (int rc = require_gpu_visible(dst, bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     // the destination's 16-byte grid; the source may be at any offset from it
-    const uint32_t head = (uint32_t)std::min<size_t>((16 - (reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u, bytes);
+    const uint32_t head = (uint32_t)grid_head(reinterpret_cast<uintptr_t>(dst), 1, bytes);
     const uint64_t nvec = (bytes - head) / 16;
     const uint32_t tail = (uint32_t)(bytes - head - nvec * 16);
     const char* s8 = static_cast<const char*>(src);
@@ -2573,31 +2530,20 @@ int mi_copy_sync(const void* src, void* dst, size_t bytes, int nontemporal, int 
         DevCtx* d = nullptr;
         int rc = get_ctx(device, &d);
         if (rc) return rc;
+        if (ks != PK_DEVICE && kd != PK_DEVICE) {  // host to host: the CPU's copy
+            memcpy(dst, src, bytes);
+            return 0;
+        }
+        DeviceScope scope;
+        if ((rc = scope.enter(d->device))) return rc;
         if (ks == PK_DEVICE && kd == PK_DEVICE) {
-            int prev = 0;
-            MI_HIP(hipGetDevice(&prev));
-            if (prev != d->device) MI_HIP(hipSetDevice(d->device));
             rc = mi_copy(src, dst, bytes, nontemporal, d->stream[0]);
             if (!rc) {
                 hipError_t e = wait_stream(d->stream[0]);
                 if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
             }
-            if (prev != d->device) (void)hipSetDevice(prev);
             return rc;
         }
-        if (ks != PK_DEVICE && kd != PK_DEVICE) {  // host to host: the CPU's copy
-            memcpy(dst, src, bytes);
-            return 0;
-        }
-        int prev = 0;
-        MI_HIP(hipGetDevice(&prev));
-        if (prev != d->device) MI_HIP(hipSetDevice(d->device));
-        struct Restore {
-            int dev, cur;
-            ~Restore() {
-                if (dev != cur) (void)hipSetDevice(dev);
-            }
-        } restore{prev, d->device};
         hipStream_t st = d->stream[0];
         if (ks == PK_PAGEABLE || kd == PK_PAGEABLE) {  // the runtime gets aligned host spans only (h2d_stage)
             rc = ensure_edges(d);
@@ -2931,20 +2877,20 @@ int mi_device_count(void) {
 int mi_set_host_mode(int mode) {
     if (mode < MI_HOST_AUTO || mode > MI_HOST_ZEROCOPY) return fail(MI_E_INVALID, "bad host mode");
     const int prev = host_mode();
-    g_host_mode.store(mode == MI_HOST_ZEROCOPY ? MI_HOST_AUTO : mode, std::memory_order_relaxed);
+    g_host_mode.set(mode == MI_HOST_ZEROCOPY ? MI_HOST_AUTO : mode);
     return prev;
 }
 
 int mi_set_sync_mode(int mode) {
     if (mode != MI_SYNC_SPIN && mode != MI_SYNC_BLOCK) return fail(MI_E_INVALID, "bad sync mode");
     const int prev = sync_mode();
-    g_sync_mode.store(mode, std::memory_order_relaxed);
+    g_sync_mode.set(mode);
     return prev;
 }
 
 int mi_set_unaligned_vectors(int on) {
     const int prev = unaligned_vectors();
-    g_unaligned.store(on ? 1 : 0, std::memory_order_relaxed);
+    g_unaligned.set(on ? 1 : 0);
     return prev;
 }
 
@@ -2977,7 +2923,7 @@ int mi_set_bcast_store(int sc1) {
 
 int mi_set_max_blocks(int mb) {
     if (mb < 0) return fail(MI_E_INVALID, "max_blocks must be >= 0");
-    g_max_blocks.store(mb, std::memory_order_relaxed);
+    g_max_blocks.set(mb);
     return 0;
 }
 

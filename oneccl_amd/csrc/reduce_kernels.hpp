@@ -19,6 +19,13 @@
 // fp16 are widened to fp32 in registers (a shift for bf16, v_cvt for fp16),
 // combined, and rounded back once per step (storage-precision chain) or
 // once at the end (fp32 accumulate).
+//
+// One place for each shared piece: fold_elem (the scalar fold of one
+// element), Tile / tile_of (a tile's descriptor geometry), head_tail (block
+// 0's scalar duty) and fan_fold (the one-wave tile fold of fan_kernel and
+// bcast_kernel).  Every kernel here is reachable from a library entry point;
+// kernels that only the measurement tools launch are in
+// tools/probe_kernels.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -532,15 +539,58 @@ __device__ __forceinline__ u32x4 pk_op4(u32x4 in, u32x4 acc) {
     return r;
 }
 
-// scalar path for one element (head/tail/misaligned)
+// ---------------------------------------------------------------------------
+// What every kernel below shares: the scalar fold of one element, the
+// geometry of one tile, and the head / tail duty of block 0.
+// ---------------------------------------------------------------------------
+
+// The scalar path (head, tail, element loop): element `idx` of the fold of
+// in[0..k), as stored.
 template <typename Tag, int OP, unsigned V>
-__device__ __forceinline__ void reduce_elem(const KArgs& a, int k, uint64_t idx) {
+__device__ __forceinline__ typename Tr<Tag>::S fold_elem(const void* const* in, int k, uint64_t idx,
+                                                         uint64_t trunc_from) {
     using S = typename Tr<Tag>::S;
     using C = typename Tr<Tag>::C;
-    const S s0 = static_cast<const S*>(a.in[0])[idx];
+    const S s0 = static_cast<const S*>(in[0])[idx];
     C acc = widen<Tag>(s0);
-    for (int i = 1; i < k; i++) acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(a.in[i])[idx]), acc);
-    static_cast<S*>(a.out)[idx] = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, a.trunc_from), s0);
+    for (int i = 1; i < k; i++) acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(in[i])[idx]), acc);
+    return native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, trunc_from), s0);
+}
+
+template <typename Tag, int OP, unsigned V>
+__device__ __forceinline__ void reduce_elem(const KArgs& a, int k, uint64_t idx) {
+    static_cast<typename Tr<Tag>::S*>(a.out)[idx] = fold_elem<Tag, OP, V>(a.in, k, idx, a.trunc_from);
+}
+
+// Tile `tile` of VECS 16-byte vectors in a body of `nvec` vectors that starts
+// `head_bytes` into every operand.  Each stream gets one buffer descriptor
+// tile_rsrc(base, byte0, bytes) per tile, so lanes past the end read zeros
+// and their stores are dropped: no guard branches.
+struct Tile {
+    uint64_t t0;     // the tile's first vector
+    uint64_t byte0;  // its byte offset from the operands' bases
+    uint32_t bytes;  // its valid bytes (0 for a tile past the end)
+    uint32_t off;    // this lane's byte offset in the tile (its first vector)
+};
+template <int VECS>
+__device__ __forceinline__ Tile tile_of(uint64_t tile, uint64_t nvec, uint64_t head_bytes) {
+    Tile t;
+    t.t0 = tile * VECS;
+    const uint64_t left = nvec > t.t0 ? nvec - t.t0 : 0;
+    t.bytes = (uint32_t)(left < (uint64_t)VECS ? left : (uint64_t)VECS) * 16u;
+    t.byte0 = head_bytes + t.t0 * 16;
+    t.off = threadIdx.x * 16u;
+    return t;
+}
+
+// The first lanes of block 0 do the scalar head [0, head) and tail
+// [tail0, tail0 + tail), fewer than 16 elements (bytes, for a copy) each.
+template <typename H, typename F>
+__device__ __forceinline__ void head_tail(uint32_t blk, H head, H tail, uint64_t tail0, F&& elem) {
+    if (blk == 0) {
+        if (threadIdx.x < head) elem(threadIdx.x);
+        if (threadIdx.x < tail) elem(tail0 + threadIdx.x);
+    }
 }
 
 // One tile row: U vectors per lane at v0, v0+B, ...  GUARD = last tile.
@@ -651,10 +701,7 @@ __global__ __launch_bounds__(B) void reduce_kernel(KArgs a) {
     }
     using S = typename Tr<Tag>::S;
     constexpr int N = 16 / sizeof(S);
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < a.head) reduce_elem<Tag, OP, V>(a, k, threadIdx.x);
-        if (threadIdx.x < a.tail) reduce_elem<Tag, OP, V>(a, k, a.head + a.nvec * N + threadIdx.x);
-    }
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N, [&](uint64_t i) { reduce_elem<Tag, OP, V>(a, k, i); });
     const uint64_t tile = (uint64_t)B * U;
     const uint64_t stride = (uint64_t)gridDim.x * tile;
     uint64_t b = blockIdx.x;
@@ -686,12 +733,8 @@ struct R2Args {
 
 template <typename Tag, int OP, unsigned V>
 __device__ __forceinline__ void reduce2_elem(const R2Args& a, uint64_t idx) {
-    using S = typename Tr<Tag>::S;
-    using C = typename Tr<Tag>::C;
-    const S s0 = static_cast<const S*>(a.acc)[idx];
-    C acc = widen<Tag>(s0);
-    acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(a.in)[idx]), acc);
-    static_cast<S*>(a.out)[idx] = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, a.trunc_from), s0);
+    const void* const in[2] = {a.acc, a.in};
+    static_cast<typename Tr<Tag>::S*>(a.out)[idx] = fold_elem<Tag, OP, V>(in, 2, idx, a.trunc_from);
 }
 
 // One tile (block `blk` of the operand set `a`): the body of reduce2_kernel,
@@ -700,6 +743,11 @@ template <typename Tag, int OP, unsigned V, int U, int B>
 __device__ __forceinline__ void reduce2_tile(const R2Args& a, uint32_t blk) {
     using S = typename Tr<Tag>::S;
     constexpr int N = 16 / sizeof(S);
+    // Head / tail and the tile's geometry are written out here, not through
+    // head_tail and tile_of: with them the bf16 RNE form took one VGPR more
+    // (40 -> 41), int64 three (9 -> 12), and the 256 MiB bf16 sum ran at
+    // 1.0007 and 1.0024 of this form's time where the same build against
+    // itself gave 0.9997 and 1.0001 (tools/ab_c2.py, profiles/fold_refactor/).
     if (blk == 0) {
         if (threadIdx.x < a.head) reduce2_elem<Tag, OP, V>(a, threadIdx.x);
         if (threadIdx.x < a.tail) reduce2_elem<Tag, OP, V>(a, a.head + a.nvec * N + threadIdx.x);
@@ -794,168 +842,122 @@ __global__ __launch_bounds__(B) void reduce2_batch_kernel(BArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// Lean K-input fan-in (compile-time K): one tile of B*U vectors per block,
-// every input's loads issued before the first combine, left fold in the
-// reference's order (acc = in[0]; acc = op(in[j], acc)).  Requires a common
-// alignment; head/tail by block 0.
-// ---------------------------------------------------------------------------
-struct RKArgs {
-    const void* in[kMaxInputs];
-    void* out;
-    uint64_t nvec;
-    uint32_t head, tail;
-    uint64_t trunc_from;
-};
-
-template <typename Tag, int OP, unsigned V, int K>
-__device__ __forceinline__ void reducek_elem(const RKArgs& a, uint64_t idx) {
-    using S = typename Tr<Tag>::S;
-    using C = typename Tr<Tag>::C;
-    const S s0 = static_cast<const S*>(a.in[0])[idx];
-    C acc = widen<Tag>(s0);
-#pragma unroll
-    for (int i = 1; i < K; i++) acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(a.in[i])[idx]), acc);
-    static_cast<S*>(a.out)[idx] = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, a.trunc_from), s0);
-}
-
-template <typename Tag, int OP, unsigned V, int K, int U, int B>
-__global__ __launch_bounds__(B) void reducek_kernel(RKArgs a) {
-    using S = typename Tr<Tag>::S;
-    constexpr int N = 16 / sizeof(S);
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < a.head) reducek_elem<Tag, OP, V, K>(a, threadIdx.x);
-        if (threadIdx.x < a.tail) reducek_elem<Tag, OP, V, K>(a, a.head + a.nvec * N + threadIdx.x);
-    }
-    const size_t hb = (size_t)a.head * sizeof(S);
-    const uint64_t v0 = (uint64_t)blockIdx.x * (B * U) + threadIdx.x;
-    const bool full = v0 + (uint64_t)(U - 1) * B < a.nvec;
-    u32x4 x[K][U];
-#pragma unroll
-    for (int i = 0; i < K; i++) {
-        const u32x4* p = reinterpret_cast<const u32x4*>(static_cast<const char*>(a.in[i]) + hb);
-#pragma unroll
-        for (int j = 0; j < U; j++)
-            if (full || v0 + (uint64_t)j * B < a.nvec) x[i][j] = vload<3>(p + v0 + (uint64_t)j * B);
-    }
-    u32x4* po = reinterpret_cast<u32x4*>(static_cast<char*>(a.out) + hb);
-#pragma unroll
-    for (int j = 0; j < U; j++) {
-        const uint64_t v = v0 + (uint64_t)j * B;
-        if (full || v < a.nvec) {
-            u32x4 xs[K];
-#pragma unroll
-            for (int i = 0; i < K; i++) xs[i] = x[i][j];
-            vstore<3>(po + v, fold_row<Tag, OP, V, K>(xs, K, a.head + v * N, a.trunc_from, [&](u32x4 (&r)[K]) {
-#pragma unroll
-                          for (int i = 0; i < K; i++)
-                              r[i] = vload<3>(reinterpret_cast<const u32x4*>(static_cast<const char*>(a.in[i]) + hb) + v);
-                      }));
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// Buffer-addressed forms (cdna_hip_programming.md T8/T20).  Each block owns one
+// One-wave fan kernels (cdna_hip_programming.md T8/T20).  Each block owns one
 // tile of B vectors.  Every stream gets one SGPR descriptor per tile, built
 // from kernel arguments and blockIdx only (wave-uniform, so no waterfall).
-// Its range is the tile's valid bytes, so in the last tile lanes past the end
-// read zeros and their stores are dropped by the range check: no guard
-// branches.  Lanes carry only a 32-bit byte offset.
+// Lanes carry only a 32-bit byte offset.
 // ---------------------------------------------------------------------------
 
-// Fan-in with a runtime K (2..kMaxInputs): all K loads are issued before the
-// first combine (uniform branches on k only), then the left fold in the
-// reference's order (acc = in[0]; acc = op(in[j], acc)).  Common alignment
-// required; head/tail by block 0 through the scalar element path.
-template <typename Tag, int OP, unsigned V, int B, int KMAX = kMaxInputs>
-__global__ __launch_bounds__(B) void fan_kernel(KArgs a) {
+// The fold of one tile, shared by fan_kernel and bcast_kernel: all k
+// (2..KMAX; bcast also 1) loads are issued before the first combine (uniform
+// branches on k only), then the left fold in the reference's order
+// (acc = in[0]; acc = op(in[j], acc)).  Returns the lane's result vector;
+// x0 = its vector of in[0] as loaded (bcast's k = 1 rule).  `ain` is the
+// kernel argument's pointer list.
+template <typename Tag, int OP, unsigned V, int KMAX>
+__device__ __forceinline__ u32x4 fan_fold(const void* const (&ain)[kMaxInputs], int k, const Tile& t,
+                                          uint64_t head, uint64_t trunc_from, u32x4& x0) {
     using S = typename Tr<Tag>::S;
     constexpr int N = 16 / sizeof(S);
-    const int k = a.k;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < a.head) reduce_elem<Tag, OP, V>(a, k, threadIdx.x);
-        if (threadIdx.x < a.tail) reduce_elem<Tag, OP, V>(a, k, a.head + a.nvec * N + threadIdx.x);
-    }
-    const uint64_t t0 = (uint64_t)blockIdx.x * B;
-    if (t0 >= a.nvec) return;
-    const uint64_t left = a.nvec - t0;
-    const uint32_t bytes = (uint32_t)(left < (uint64_t)B ? left : (uint64_t)B) * 16u;
-    const uint64_t byte0 = a.head * sizeof(S) + t0 * 16;
-    const uint32_t off = threadIdx.x * 16u;
     // Materialise every input pointer before the first branch: left alone, the
     // compiler sinks each kernarg load into its `i < k` block and every buffer
     // load then waits on its own scalar load.
     const void* in[KMAX];
 #pragma unroll
     for (int i = 0; i < KMAX; i++) {
-        in[i] = a.in[i];
+        in[i] = ain[i];
         asm volatile("" ::"s"(in[i]));
     }
     u32x4 x[KMAX];
 #pragma unroll
     for (int i = 0; i < KMAX; i++)
-        if (i < k) x[i] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(in[i], byte0, bytes), off, 0, kAuxNT);
+        if (i < k) x[i] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(in[i], t.byte0, t.bytes), t.off, 0, kAuxNT);
+    x0 = x[0];
     if constexpr (packed_int<Tag>()) {
         u32x4 r = x[0];
 #pragma unroll
         for (int i = 1; i < KMAX; i++)
             if (i < k) r = pk_op4<Tag, OP>(x[i], r);
-        __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out, byte0, bytes), off, 0, kAuxNT);
-        return;
-    }
-    // The fast fold is written out here rather than through fold_vec: with
-    // the runtime-k loop in a callee, the compiler kept the fp32 8-input
-    // form's x[] as an aggregate and spilled it to scratch (33 ms instead of
-    // 1.6 ms per GiB; tests/test_kernel_resources.py guards every kernel).
-    using C = typename Tr<Tag>::C;
-    C acc[N];
-    const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x[0]);
+        return r;
+    } else {
+        // The fast fold is written out here rather than through fold_vec: with
+        // the runtime-k loop in a callee, the compiler kept the fp32 8-input
+        // form's x[] as an aggregate and spilled it to scratch (33 ms instead of
+        // 1.6 ms per GiB; tests/test_kernel_resources.py guards every kernel).
+        using C = typename Tr<Tag>::C;
+        C acc[N];
+        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x[0]);
 #pragma unroll
-    for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
+        for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
 #pragma unroll
-    for (int i = 1; i < KMAX; i++) {
-        if (i < k) {
-            const Pack<S> pi = __builtin_bit_cast(Pack<S>, x[i]);
+        for (int i = 1; i < KMAX; i++) {
+            if (i < k) {
+                const Pack<S> pi = __builtin_bit_cast(Pack<S>, x[i]);
 #pragma unroll
-            for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V, false>(widen<Tag>(pi.e[e]), acc[e]);
+                for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V, false>(widen<Tag>(pi.e[e]), acc[e]);
+            }
         }
-    }
-    Pack<S> pr;
-    const uint64_t e0 = a.head + (t0 + threadIdx.x) * N;
+        Pack<S> pr;
+        const uint64_t e0 = head + (t.t0 + threadIdx.x) * N;
 #pragma unroll
-    for (int e = 0; e < N; e++) pr.e[e] = finish_fold<Tag, V, false>(acc[e], e0 + e, a.trunc_from);
-    __builtin_amdgcn_raw_buffer_store_b128(
-        x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, a.trunc_from),
-        tile_rsrc(a.out, byte0, bytes), off, 0, kAuxNT);
+        for (int e = 0; e < N; e++) pr.e[e] = finish_fold<Tag, V, false>(acc[e], e0 + e, trunc_from);
+        return x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, trunc_from);
+    }
 }
 
-// The 2-input form of the same (R2Args: acc, in -> out).
-template <typename Tag, int OP, unsigned V, int B>
-__global__ __launch_bounds__(B) void reduce2b_kernel(R2Args a) {
-    using S = typename Tr<Tag>::S;
-    constexpr int N = 16 / sizeof(S);
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < a.head) reduce2_elem<Tag, OP, V>(a, threadIdx.x);
-        if (threadIdx.x < a.tail) reduce2_elem<Tag, OP, V>(a, a.head + a.nvec * N + threadIdx.x);
+// Fan-in with a runtime K (2..kMaxInputs).  Common alignment required;
+// head/tail by block 0 through the scalar element path.
+template <typename Tag, int OP, unsigned V, int B, int KMAX = kMaxInputs>
+__global__ __launch_bounds__(B) void fan_kernel(KArgs a) {
+    constexpr int N = 16 / sizeof(typename Tr<Tag>::S);
+    const int k = a.k;
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N, [&](uint64_t i) { reduce_elem<Tag, OP, V>(a, k, i); });
+    const Tile t = tile_of<B>(blockIdx.x, a.nvec, a.head * sizeof(typename Tr<Tag>::S));
+    if (t.t0 >= a.nvec) return;
+    if constexpr (std::is_same<Tag, fp16_tag>::value) {
+        // fp16 keeps fan_fold's text written out in the kernel.  Through the
+        // callee its forms took 6-9 VGPRs more (46 -> 53, 48 -> 57, 78 -> 85,
+        // 81 -> 89) and the 8-input 256 MiB sum ran at 1.0035 of this form's
+        // time, every one of 12 placements at or above 1.0000, where the same
+        // build against itself gave 0.9986 (tools/ab_c2.py,
+        // profiles/fold_refactor/).  Not the cause, each tried alone: the
+        // element index, head_tail, Tile, the returned x[0], reference or value
+        // parameters, the store passed in as a functor.
+        using S = uint16_t;
+        const void* in[KMAX];
+#pragma unroll
+        for (int i = 0; i < KMAX; i++) {
+            in[i] = a.in[i];
+            asm volatile("" ::"s"(in[i]));
+        }
+        u32x4 x[KMAX];
+#pragma unroll
+        for (int i = 0; i < KMAX; i++)
+            if (i < k) x[i] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(in[i], t.byte0, t.bytes), t.off, 0, kAuxNT);
+        float acc[N];
+        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x[0]);
+#pragma unroll
+        for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
+#pragma unroll
+        for (int i = 1; i < KMAX; i++) {
+            if (i < k) {
+                const Pack<S> pi = __builtin_bit_cast(Pack<S>, x[i]);
+#pragma unroll
+                for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V, false>(widen<Tag>(pi.e[e]), acc[e]);
+            }
+        }
+        Pack<S> pr;
+        const uint64_t e0 = a.head + (t.t0 + threadIdx.x) * N;
+#pragma unroll
+        for (int e = 0; e < N; e++) pr.e[e] = finish_fold<Tag, V, false>(acc[e], e0 + e, a.trunc_from);
+        __builtin_amdgcn_raw_buffer_store_b128(
+            x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, a.trunc_from),
+            tile_rsrc(a.out, t.byte0, t.bytes), t.off, 0, kAuxNT);
+    } else {
+        u32x4 x0;
+        const u32x4 r = fan_fold<Tag, OP, V, KMAX>(a.in, k, t, a.head, a.trunc_from, x0);
+        __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out, t.byte0, t.bytes), t.off, 0, kAuxNT);
     }
-    const uint64_t t0 = (uint64_t)blockIdx.x * B;
-    if (t0 >= a.nvec) return;
-    const uint64_t left = a.nvec - t0;
-    const uint32_t bytes = (uint32_t)(left < (uint64_t)B ? left : (uint64_t)B) * 16u;
-    const uint64_t byte0 = (uint64_t)a.head * sizeof(S) + t0 * 16;
-    const uint32_t off = threadIdx.x * 16u;
-    const u32x4 xs[2] = {__builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.acc, byte0, bytes), off, 0, kAuxNT),
-                         __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in, byte0, bytes), off, 0, kAuxNT)};
-    const uint64_t e0 = a.head + (t0 + threadIdx.x) * N;
-    __builtin_amdgcn_raw_buffer_store_b128(
-        fold_row<Tag, OP, V, 2>(xs, 2, e0, a.trunc_from,
-                                [&](u32x4 (&r)[2]) {
-                                    r[0] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.acc, byte0, bytes), off, 0,
-                                                                                 kAuxNT);
-                                    r[1] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in, byte0, bytes), off, 0,
-                                                                                 kAuxNT);
-                                }),
-        tile_rsrc(a.out, byte0, bytes), off, 0, kAuxNT);
 }
 
 // ---------------------------------------------------------------------------
@@ -964,7 +966,7 @@ __global__ __launch_bounds__(B) void reduce2b_kernel(R2Args a) {
 // allreduce_kernel_* (out = peer_out = op(in, peer_in),
 // src/kernels/kernels.cl:190-217) and as reduce_monolithic_kernel_N followed
 // by write_monolithic_kernel_N (kernels.cl:269-421, 424-560).  The fold is
-// fan_kernel's, bit for bit; the vector grid is the outputs' common 16-byte
+// fan_fold, the one fan_kernel runs; the vector grid is the outputs' common 16-byte
 // grid.  An output may be exactly one of the inputs (in place): such an input
 // has the outputs' misalignment, so a lane loads exactly the bytes it later
 // stores, and every lane has all k loads back (the refold keeps them in
@@ -994,90 +996,39 @@ constexpr bool bcast_copies_k1() {
 template <typename Tag, int OP, unsigned V>
 __device__ __forceinline__ void bcast_elem(const BCArgs& a, int k, int m, uint64_t idx) {
     using S = typename Tr<Tag>::S;
-    using C = typename Tr<Tag>::C;
-    const S s0 = static_cast<const S*>(a.in[0])[idx];
-    C acc = widen<Tag>(s0);
-    for (int i = 1; i < k; i++) acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(a.in[i])[idx]), acc);
-    S r = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, a.trunc_from), s0);
-    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? s0 : r;
+    S r = fold_elem<Tag, OP, V>(a.in, k, idx, a.trunc_from);
+    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? static_cast<const S*>(a.in[0])[idx] : r;
     for (int o = 0; o < m; o++) static_cast<S*>(a.out[o])[idx] = r;
 }
 
 // Shared tail of the two kernels below: the m stores of a lane's result, a
 // wave-uniform loop over the output pointers (one descriptor per iteration,
 // read from the kernel arguments by a uniform index: no per-lane array).
-__device__ __forceinline__ void bcast_store(const BCArgs& a, int m, u32x4 r, uint64_t byte0, uint32_t bytes,
-                                            uint32_t off) {
+__device__ __forceinline__ void bcast_store(const BCArgs& a, int m, u32x4 r, const Tile& t) {
     if (a.store_sc1) {
 #pragma nounroll
         for (int o = 0; o < m; o++)
-            __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out[o], byte0, bytes), off, 0, kAuxSC1NT);
+            __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out[o], t.byte0, t.bytes), t.off, 0, kAuxSC1NT);
     } else {
 #pragma nounroll
         for (int o = 0; o < m; o++)
-            __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out[o], byte0, bytes), off, 0, kAuxNT);
+            __builtin_amdgcn_raw_buffer_store_b128(r, tile_rsrc(a.out[o], t.byte0, t.bytes), t.off, 0, kAuxNT);
     }
 }
 
-// One tile of B vectors per block, every stream through one buffer descriptor
-// per tile (range = the tile's valid bytes: lanes past the end load zeros and
-// their stores are dropped, no guard branches).  All k loads are issued before
-// the first combine, then fan_kernel's fold, then the m stores.
+// One tile of B vectors per block: fan_fold (all k loads before the first
+// combine), then the m stores.
 template <typename Tag, int OP, unsigned V, int B, int KMAX>
 __global__ __launch_bounds__(B) void bcast_kernel(BCArgs a) {
-    using S = typename Tr<Tag>::S;
-    constexpr int N = 16 / sizeof(S);
+    constexpr int N = 16 / sizeof(typename Tr<Tag>::S);
     const int k = a.k, m = a.m;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < a.head) bcast_elem<Tag, OP, V>(a, k, m, threadIdx.x);
-        if (threadIdx.x < a.tail) bcast_elem<Tag, OP, V>(a, k, m, a.head + a.nvec * N + threadIdx.x);
-    }
-    const uint64_t t0 = (uint64_t)blockIdx.x * B;
-    if (t0 >= a.nvec) return;
-    const uint64_t left = a.nvec - t0;
-    const uint32_t bytes = (uint32_t)(left < (uint64_t)B ? left : (uint64_t)B) * 16u;
-    const uint64_t byte0 = a.head * sizeof(S) + t0 * 16;
-    const uint32_t off = threadIdx.x * 16u;
-    // every input pointer before the first branch, as in fan_kernel
-    const void* in[KMAX];
-#pragma unroll
-    for (int i = 0; i < KMAX; i++) {
-        in[i] = a.in[i];
-        asm volatile("" ::"s"(in[i]));
-    }
-    u32x4 x[KMAX];
-#pragma unroll
-    for (int i = 0; i < KMAX; i++)
-        if (i < k) x[i] = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(in[i], byte0, bytes), off, 0, kAuxNT);
-    u32x4 r;
-    if constexpr (packed_int<Tag>()) {
-        r = x[0];
-#pragma unroll
-        for (int i = 1; i < KMAX; i++)
-            if (i < k) r = pk_op4<Tag, OP>(x[i], r);
-    } else {
-        // written out, not through fold_vec: see fan_kernel on scratch
-        using C = typename Tr<Tag>::C;
-        C acc[N];
-        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x[0]);
-#pragma unroll
-        for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
-#pragma unroll
-        for (int i = 1; i < KMAX; i++) {
-            if (i < k) {
-                const Pack<S> pi = __builtin_bit_cast(Pack<S>, x[i]);
-#pragma unroll
-                for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V, false>(widen<Tag>(pi.e[e]), acc[e]);
-            }
-        }
-        Pack<S> pr;
-        const uint64_t e0 = a.head + (t0 + threadIdx.x) * N;
-#pragma unroll
-        for (int e = 0; e < N; e++) pr.e[e] = finish_fold<Tag, V, false>(acc[e], e0 + e, a.trunc_from);
-        r = x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, a.trunc_from);
-        if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x[0] : r;
-    }
-    bcast_store(a, m, r, byte0, bytes, off);
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N, [&](uint64_t i) { bcast_elem<Tag, OP, V>(a, k, m, i); });
+    const Tile t = tile_of<B>(blockIdx.x, a.nvec, a.head * sizeof(typename Tr<Tag>::S));
+    if (t.t0 >= a.nvec) return;
+    u32x4 x0;
+    u32x4 r = fan_fold<Tag, OP, V, KMAX>(a.in, k, t, a.head, a.trunc_from, x0);
+    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x0 : r;
+    bcast_store(a, m, r, t);
 }
 
 // The grid-stride form, for launches under mi_set_max_blocks and for the
@@ -1097,18 +1048,15 @@ __global__ __launch_bounds__(B) void bcast_stride_kernel(BCArgs a) {
             bcast_elem<Tag, OP, V>(a, k, m, i);
         return;
     }
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < a.head) bcast_elem<Tag, OP, V>(a, k, m, threadIdx.x);
-        if (threadIdx.x < a.tail) bcast_elem<Tag, OP, V>(a, k, m, a.head + a.nvec * N + threadIdx.x);
-    }
-    const uint32_t off = threadIdx.x * 16u;
-    for (uint64_t t0 = (uint64_t)blockIdx.x * B; t0 < a.nvec; t0 += (uint64_t)gridDim.x * B) {
-        const uint64_t left = a.nvec - t0;
-        const uint32_t bytes = (uint32_t)(left < (uint64_t)B ? left : (uint64_t)B) * 16u;
-        const uint64_t byte0 = a.head * sizeof(S) + t0 * 16;
-        const u32x4 x0 = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[0], byte0, bytes), off, 0, kAuxNT);
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N, [&](uint64_t i) { bcast_elem<Tag, OP, V>(a, k, m, i); });
+    for (uint64_t tile = blockIdx.x; tile * B < a.nvec; tile += gridDim.x) {
+        const Tile t = tile_of<B>(tile, a.nvec, a.head * sizeof(S));
+        const auto load = [&](int i) {
+            return __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[i], t.byte0, t.bytes), t.off, 0, kAuxNT);
+        };
+        const u32x4 x0 = load(0);
         u32x4 cur = x0, r = x0;
-        if (k >= 2) cur = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[1], byte0, bytes), off, 0, kAuxNT);
+        if (k >= 2) cur = load(1);
         using C = typename Tr<Tag>::C;
         C acc[N];
         const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x0);
@@ -1118,8 +1066,7 @@ __global__ __launch_bounds__(B) void bcast_stride_kernel(BCArgs a) {
         }
         for (int i = 1; i < k; i++) {
             u32x4 nxt = cur;
-            if (i + 1 < k)
-                nxt = __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[i + 1], byte0, bytes), off, 0, kAuxNT);
+            if (i + 1 < k) nxt = load(i + 1);
             if constexpr (packed_int<Tag>()) {
                 r = pk_op4<Tag, OP>(cur, r);
             } else {
@@ -1131,14 +1078,14 @@ __global__ __launch_bounds__(B) void bcast_stride_kernel(BCArgs a) {
         }
         if constexpr (!packed_int<Tag>()) {
             Pack<S> pr;
-            const uint64_t e0 = a.head + (t0 + threadIdx.x) * N;
+            const uint64_t e0 = a.head + (t.t0 + threadIdx.x) * N;
 #pragma unroll
             for (int e = 0; e < N; e++)
                 pr.e[e] = native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc[e], e0 + e, a.trunc_from), p0.e[e]);
             r = __builtin_bit_cast(u32x4, pr);
             if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x0 : r;
         }
-        bcast_store(a, m, r, byte0, bytes, off);
+        bcast_store(a, m, r, t);
     }
 }
 
@@ -1302,13 +1249,7 @@ __global__ __launch_bounds__(B) void convert_kernel(CArgs a) {
 template <int MEM>
 __global__ __launch_bounds__(kBlock) void copy_kernel(const char* __restrict__ src8, char* __restrict__ dst8,
                                                       uint32_t head, uint64_t nvec, uint32_t tail) {
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < head) dst8[threadIdx.x] = src8[threadIdx.x];
-        if (threadIdx.x < tail) {
-            const uint64_t o = head + nvec * 16 + threadIdx.x;
-            dst8[o] = src8[o];
-        }
-    }
+    head_tail(blockIdx.x, head, tail, head + nvec * 16, [&](uint64_t o) { dst8[o] = src8[o]; });
     const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(src8 + head);
     u32x4* __restrict__ dst = reinterpret_cast<u32x4*>(dst8 + head);
     constexpr int U = 4;
@@ -1340,25 +1281,16 @@ constexpr int kCopyBlock = 64;
 template <int MEM, int B = kCopyBlock>
 __global__ __launch_bounds__(B) void copy_lean_kernel(const char* __restrict__ src8, char* __restrict__ dst8,
                                                       uint32_t head, uint64_t nvec, uint32_t tail) {
-    if (blockIdx.x == 0) {
-        if (threadIdx.x < head) dst8[threadIdx.x] = src8[threadIdx.x];
-        if (threadIdx.x < tail) {
-            const uint64_t o = head + nvec * 16 + threadIdx.x;
-            dst8[o] = src8[o];
-        }
-    }
-    const uint64_t t0 = (uint64_t)blockIdx.x * B;
-    const uint64_t v = t0 + threadIdx.x;
+    head_tail(blockIdx.x, head, tail, head + nvec * 16, [&](uint64_t o) { dst8[o] = src8[o]; });
+    const uint64_t v = (uint64_t)blockIdx.x * B + threadIdx.x;
     if (MEM & 4) {
         // global nt loads: buffer loads here ran 0.4-0.7 % slower in every
         // one of 20 fresh placements (tools/ab_c2.py --config copy,
         // profiles/round6_run8/), unlike the 2-input reduce's
-        const uint64_t tleft = nvec > t0 ? nvec - t0 : 0;
-        const uint32_t tbytes = (uint32_t)(tleft < (uint64_t)B ? tleft : (uint64_t)B) * 16u;
-        const __amdgpu_buffer_rsrc_t o = tile_rsrc(dst8 + head, t0 * 16, tbytes);
+        const Tile t = tile_of<B>(blockIdx.x, nvec, head);
         if (v < nvec)
-            __builtin_amdgcn_raw_buffer_store_b128(vload<MEM & 1>(reinterpret_cast<const u32x4*>(src8 + head) + v), o,
-                                                   threadIdx.x * 16u, 0, kAuxSC1NT);
+            __builtin_amdgcn_raw_buffer_store_b128(vload<MEM & 1>(reinterpret_cast<const u32x4*>(src8 + head) + v),
+                                                   tile_rsrc(dst8, t.byte0, t.bytes), t.off, 0, kAuxSC1NT);
     } else if (v < nvec) {
         vstore<MEM & 2>(reinterpret_cast<u32x4*>(dst8 + head) + v,
                         vload<MEM & 1>(reinterpret_cast<const u32x4*>(src8 + head) + v));

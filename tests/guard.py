@@ -38,8 +38,11 @@ mi_reduce.hip and host_reduce*.cpp; knob = how the test routes to it):
   copy_lean_kernel<1 / 3>  test_gpu_bounds::test_copy_kernels (mi_copy, ccl_comp_copy; nontemporal 0 / 1)
   copy_kernel<1 / 3>       test_gpu_bounds::test_copy_kernels (mi_set_max_blocks(3))
   copy_lean_kernel<5>      test_gpu_shim::test_comp_copy_streaming_sizes (copies of 64 MiB and more)
-  reducek_kernel,          launched by tools/reduce_sweep.hip only: no library entry point reaches them
-  reduce2b_kernel
+  bcast_kernel<.., 8 / 16> test_gpu_bcast_bounds::test_tile_kernel, _in_place, _fp32_accumulate (mi_reduce_bcast;
+                           fan_fold, the fold fan_kernel runs)
+  bcast_stride_kernel      test_gpu_bcast_bounds::test_stride_kernel_under_grid_cap, test_element_loop_*
+  reducek_kernel,          tools/probe_kernels.hpp, launched by tools/reduce_sweep.hip only: not in the
+  reduce2b_kernel          product header, no library entry point reaches them
   bucket / tmp_buf layouts test_gpu_bounds::test_contiguous_ragged_chunks_in_one_bucket, test_packed_tmp_buf
   zero-copy (pinned)       test_gpu_host_bounds::test_zero_copy_pinned (mi_reduce_sync, mi_reduce_multi_sync)
   bounce buffers           test_gpu_host_bounds::test_bounce_buffers (pageable, at most 1 MiB)

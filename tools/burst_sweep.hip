@@ -24,7 +24,7 @@
 #include <string>
 #include <vector>
 
-#include "../oneccl_amd/csrc/reduce_kernels.hpp"
+#include "probe_kernels.hpp"
 
 using namespace mi;
 

@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "../oneccl_amd/csrc/reduce_kernels.hpp"
+#include "probe_kernels.hpp"
 
 using namespace mi;
 
