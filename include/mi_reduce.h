@@ -165,6 +165,56 @@ int mi_reduce_multi(const void* const* inputs, int k, void* out, size_t count,
 int mi_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m,
                     size_t count, int dtype, int op, unsigned flags, void* stream);
 
+/* mi_reduce_bcast of a sum with one multiply before the final rounding: the
+ * mean over ranks, or the sum under a loss-scale or gradient-accumulation
+ * factor, in the pass that completes the allreduce.  The reference's
+ * reduction enum has no average (include/oneapi/ccl/types.hpp:41-47), so its
+ * callers scale in a second pass over every output: k + 3m buffer-sized
+ * streams and 1 + m dispatches where this moves k + m in one.
+ *   Let U be what mi_reduce_bcast stores for the same inputs, k, count, dtype,
+ * op and flags, and A the compute-type accumulator just before the final
+ * conversion to storage: A = U for fp32 and fp64; A = widen(U) for bf16 and
+ * fp16 without MI_F_ACC_FP32 (every step has already rounded to storage; for
+ * k = 1, U is inputs[0]'s bytes); the fp32 accumulator of the fold, before
+ * its one rounding, for bf16 and fp16 with MI_F_ACC_FP32.  Let s = (float)scale
+ * (round to nearest even) for fp32, bf16 and fp16, s = scale for fp64.  Then
+ * for every i < m
+ *     outs[i][e] = U[e]              where A[e] is a NaN,
+ *     outs[i][e] = narrow(A[e] * s)  otherwise.
+ * A NaN is stored exactly as the unscaled call stores it and the multiply is
+ * skipped, so NaN bits depend on no multiplier's NaN propagation.  The
+ * multiply is one IEEE-754 multiply in the compute type, round to nearest
+ * even, denormals kept.  narrow is the final conversion the unscaled fold uses
+ * under `flags`: bf16 truncation, or round to nearest even with
+ * VCVTNEPS2BF16's denormal-to-zero (MI_F_BF16_RNE), the truncated
+ * MI_F_BF16_TAIL_TRUNC16 tail; fp16 round to nearest even.  Under
+ * MI_F_ACC_FP32 the product is rounded once, where a second pass rounds the
+ * sum and then the product.
+ *   scale == 1.0 is not special-cased.  It gives U everywhere except where
+ * narrow(widen(x)) != x, which happens only to bf16 denormals passing through
+ * k = 1 under MI_F_BF16_RNE (flushed to signed zero).
+ *   Supported: op == MI_OP_SUM on fp16, bf16, fp32 and fp64, every MI_F_*
+ * variant valid for a sum.  MI_E_UNSUPPORTED with a message naming the
+ * argument: another op (a scaled product, minimum or maximum has no caller),
+ * an integer dtype.  MI_E_INVALID, before any HIP call, besides every refusal
+ * of mi_reduce_bcast: a scale that is NaN or infinite, and an s that is zero
+ * or infinite after the conversion above (1e-60 and 1e300 for a float compute
+ * type), since inf * 0 would make a NaN whose bits differ between targets.
+ * count == 0 returns 0 after the checks.
+ *   As mi_reduce_bcast: the same aliasing rules (an output may be exactly one
+ * of the inputs; outs[i] == inputs[i] for all i is the in-place averaged
+ * allreduce, safe because a lane still has all k loads back before its first
+ * store), 1 <= k, m <= MI_MAX_INPUTS, device or device-visible pinned
+ * pointers (a pageable operand is refused), asynchronous on `stream`, one
+ * kernel node in a HIP graph.  Every (k, m), m = 1 and k = 1 included, runs
+ * the fan-out kernels.
+ *   Not provided: a _sync, staged or pageable form, a request form, a host-CPU
+ * path, a drop-in C++ symbol or a patch under integration/ (the reference has
+ * no scaled reduction to replace).                                          */
+int mi_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, int m,
+                           size_t count, int dtype, int op, unsigned flags,
+                           double scale, void* stream);
+
 /* n independent mi_reduce calls in one dispatch: descs[i].inout =
  * op(descs[i].in, descs[i].inout) over descs[i].count elements, all with one
  * dtype / op / flags.  Results are those of the n mi_reduce calls in any
@@ -416,7 +466,9 @@ int mi_get_residency(int device, int k, int* waves_per_cu, unsigned* lds_bytes);
  * tools/residency_ab.py A/Bs the plan against other residencies with it.
  * A mi_reduce_bcast launch of k inputs and m >= 2 outputs is planned by its
  * streams in flight per wave, s = min(k + m - 1, 16): the fan-in's plan for
- * s inputs up to 12, 6 waves above; mi_set_residency(s, ...) overrides it. */
+ * s inputs up to 12, 6 waves above; mi_set_residency(s, ...) overrides it.
+ * mi_reduce_bcast_scaled plans every (k, m) that way, m = 1 included, but
+ * (2, 1), which takes the 2-input kernel's plan (k = 2 above).              */
 int mi_set_residency(int k, int waves_per_cu);
 /* Store policy of mi_reduce_bcast's vector stores (tuning knob): 1 (default)
  * = sc1 + nt, as the 2-input kernel stores (the line leaves L2 as it is

@@ -162,14 +162,12 @@ def reduce_multi(inputs: Sequence, out, op: reduction = reduction.sum, flags: Op
                                _stream_handle(stream)), "mi_reduce_multi")
 
 
-def reduce_bcast(inputs: Sequence, outs: Sequence, op: reduction = reduction.sum, flags: Optional[int] = None,
-                 stream=None) -> None:
-    """Every tensor of `outs` = the left fold over `inputs` (as reduce_multi),
-    folded once and written to all of them in one pass (mi_reduce_bcast).  An
-    output may be one of the inputs; two outputs may not overlap."""
+def _bcast_args(inputs: Sequence, outs: Sequence, flags: Optional[int], what: str):
+    """The tensor checks reduce_bcast and reduce_bcast_scaled share:
+    (inputs, outs, dtype, count, flags)."""
     inputs, outs = list(inputs), list(outs)
     if not inputs or not outs:
-        raise ValueError("reduce_bcast needs at least one input and one output")
+        raise ValueError(f"{what} needs at least one input and one output")
     t0 = inputs[0]
     for t in inputs + outs:
         if t.dtype != t0.dtype:
@@ -179,10 +177,31 @@ def reduce_bcast(inputs: Sequence, outs: Sequence, op: reduction = reduction.sum
         if t.numel() != t0.numel():
             raise ValueError(f"all tensors must have the same numel ({t.numel()} against {t0.numel()})")
     dt, count = _dev_args(inputs + outs, None)
-    f = reference_flags(dt) if flags is None else flags
+    return inputs, outs, dt, count, reference_flags(dt) if flags is None else flags
+
+
+def reduce_bcast(inputs: Sequence, outs: Sequence, op: reduction = reduction.sum, flags: Optional[int] = None,
+                 stream=None) -> None:
+    """Every tensor of `outs` = the left fold over `inputs` (as reduce_multi),
+    folded once and written to all of them in one pass (mi_reduce_bcast).  An
+    output may be one of the inputs; two outputs may not overlap."""
+    inputs, outs, dt, count, f = _bcast_args(inputs, outs, flags, "reduce_bcast")
     check(mi().mi_reduce_bcast(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs),
                                void_ptr_array([t.data_ptr() for t in outs]), len(outs), count, int(dt), int(op), f,
                                _stream_handle(stream)), "mi_reduce_bcast")
+
+
+def reduce_bcast_scaled(inputs: Sequence, outs: Sequence, scale: float, flags: Optional[int] = None,
+                        stream=None) -> None:
+    """Every tensor of `outs` = the sum over `inputs` times `scale`, the
+    multiply applied once to the accumulator before its final rounding
+    (mi_reduce_bcast_scaled; scale = 1 / len(inputs) is the mean).  Floating
+    tensors only; aliasing as reduce_bcast."""
+    inputs, outs, dt, count, f = _bcast_args(inputs, outs, flags, "reduce_bcast_scaled")
+    check(mi().mi_reduce_bcast_scaled(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs),
+                                      void_ptr_array([t.data_ptr() for t in outs]), len(outs), count, int(dt),
+                                      int(reduction.sum), f, float(scale), _stream_handle(stream)),
+          "mi_reduce_bcast_scaled")
 
 
 # ---- the drop-in shim (synchronous, host or device pointers) ------------
@@ -279,7 +298,7 @@ def shard_range(count: int, rank: int, world: int, align: int = 256) -> tuple[in
 
 
 __all__ = ["reduction", "datatype", "bf16_impl", "fp16_impl", "reduce", "reduce_out", "reduce_multi",
-           "reduce_bcast",
+           "reduce_bcast", "reduce_bcast_scaled",
            "comp_reduce", "comp_reduce_start", "comp_batch_reduce_start", "comp_request", "comp_batch_reduce", "comp_copy", "reduction_to_str", "impl_types", "env_reload",
            "shard_range", "bf16_flags", "fp16_flags", "reference_flags", "F_MINMAX_INOUT_FIRST", "F_BF16_RNE",
            "F_ACC_FP32", "F_BF16_TAIL_TRUNC16", "DTYPE_SIZE", "_lib"]

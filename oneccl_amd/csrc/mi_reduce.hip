@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <deque>
@@ -163,6 +164,7 @@ typedef hipError_t (*LaunchFanFn)(hipStream_t, const KArgs&, unsigned lds);
 typedef hipError_t (*Launch2Fn)(dim3, hipStream_t, const R2Args&, unsigned lds);
 typedef hipError_t (*LaunchBFn)(dim3, hipStream_t, const BArgs&, unsigned lds);
 typedef hipError_t (*LaunchBcFn)(unsigned stride_blocks, hipStream_t, const BCArgs&, unsigned lds);
+typedef hipError_t (*LaunchBcScFn)(unsigned stride_blocks, hipStream_t, const BCArgs&, const ScaleArg&, unsigned lds);
 
 // Lean 2-input kernel shape: one 16-byte vector per lane, one-wave (64-lane)
 // tiles, 21 waves resident per CU (capped by idle LDS, as the fan-in below).
@@ -314,15 +316,37 @@ hipError_t launch_bcast(unsigned stride_blocks, hipStream_t s, const BCArgs& a, 
     return hipGetLastError();
 }
 
+// mi_reduce_bcast_scaled: launch_bcast's routing onto the kernels with a multiplier.
+template <typename Tag, int OP, unsigned V>
+hipError_t launch_bcast_scaled(unsigned stride_blocks, hipStream_t s, const BCArgs& a, const ScaleArg& sc,
+                               unsigned lds) {
+    if (stride_blocks) {
+        hipLaunchKernelGGL((bcast_scaled_stride_kernel<Tag, OP, V, kBlock>), dim3(stride_blocks), dim3(kBlock), 0,
+                           s, a, sc);
+        return hipGetLastError();
+    }
+    constexpr int B = kBcastBlock;
+    const uint64_t blocks = std::max<uint64_t>((a.nvec + B - 1) / B, 1);
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidConfiguration;
+    if (a.k <= 8)
+        hipLaunchKernelGGL((bcast_scaled_kernel<Tag, OP, V, B, 8>), dim3((unsigned)blocks), dim3(B), lds, s, a, sc);
+    else
+        hipLaunchKernelGGL((bcast_scaled_kernel<Tag, OP, V, B, kMaxInputs>), dim3((unsigned)blocks), dim3(B), lds, s,
+                           a, sc);
+    return hipGetLastError();
+}
+
 // general: any K (runtime), grid-stride, also the element loop for operands
 // with different misalignments; lean: K = 2 with a common alignment; fan:
-// any other K with a common alignment; bcast: the fold written to M outputs
+// any other K with a common alignment; bcast: the fold written to M outputs;
+// bcast_scaled: that under a multiplier (sum of a floating type only)
 struct Kern {
     LaunchFn general = nullptr;
     Launch2Fn lean = nullptr;
     LaunchFanFn fan = nullptr;
     LaunchBFn batch = nullptr;
     LaunchBcFn bcast = nullptr;
+    LaunchBcScFn bcast_scaled = nullptr;
 };
 
 template <typename Tag, int OP, unsigned V>
@@ -346,6 +370,7 @@ Kern entry() {
         k.fan = &launch_fan<Tag, OP, V>;
         k.batch = &launch_batch<Tag, OP, V>;
         k.bcast = &launch_bcast<Tag, OP, V>;
+        if constexpr (OP == OP_SUM && Tr<Tag>::fp) k.bcast_scaled = &launch_bcast_scaled<Tag, OP, V>;
     }
     return k;
 }
@@ -755,29 +780,30 @@ int check_bcast_args(const void* const* inputs, int k, void* const* outs, int m,
     return 0;
 }
 
-int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt, int op,
-                        unsigned flags, hipStream_t stream) {
-    size_t es;
-    if (int rc = check_dtype(dt, &es)) return rc;
-    if (int rc = check_op(op)) return rc;
+int check_bcast_lists(const void* const* inputs, int k, void* const* outs, int m) {
     if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count k out of range [1,16]");
     if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
     if (!inputs) return fail(MI_E_INVALID, "null input list");
     if (!outs) return fail(MI_E_INVALID, "null output list");
-    if (int rc = check_bcast_args(inputs, k, outs, m, count, es)) return rc;
-    if (count == 0) return 0;
-    // one output: mi_reduce_multi, its kernels and launch plans
-    if (m == 1) return launch_reduce(inputs, k, outs[0], count, dt, op, flags, stream);
+    return 0;
+}
 
+int require_bcast_visible(const void* const* inputs, int k, void* const* outs, int m, size_t bytes) {
     for (int i = 0; i < k; i++)
-        if (int rc = require_gpu_visible(inputs[i], count * es)) return rc;
+        if (int rc = require_gpu_visible(inputs[i], bytes)) return rc;
     for (int i = 0; i < m; i++)
-        if (int rc = require_gpu_visible(outs[i], count * es)) return rc;
+        if (int rc = require_gpu_visible(outs[i], bytes)) return rc;
+    return 0;
+}
 
-    const unsigned v = canon_flags(dt, op, flags, k);
-    const Kern kern = pick(dt, op, v);
-    if (!kern.bcast) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
-
+// What mi_reduce_bcast and mi_reduce_bcast_scaled share once their arguments
+// have passed and their kernel is picked: the outputs' common 16-byte grid,
+// the residency cap (`waves` per CU), the store policy and the grid-cap
+// routing.  launch(stride_blocks, args, lds) starts the kernel (launch_bcast's
+// convention).
+template <typename Launch>
+int issue_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, size_t es,
+                hipStream_t stream, int waves, Launch&& launch) {
     // the outputs' common 16-byte grid (vec_grid.hpp)
     const VecGrid g = plan_vec_grid(es, count, outs, m, inputs, k, unaligned_vectors() != 0);
 
@@ -797,11 +823,76 @@ int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int
     const int cap = max_blocks();
     hipError_t e;
     if (g.vec && cap == 0 && g.nvec / kBcastBlock < 0x7FFFFFFFull)
-        e = kern.bcast(0, stream, a, wave_cap_lds(stream, bcast_planned_waves(k, m)));
+        e = launch(0u, a, wave_cap_lds(stream, waves));
     else
-        e = kern.bcast(stride_grid(g, kBlock, count, cap), stream, a, 0);
+        e = launch(stride_grid(g, kBlock, count, cap), a, 0u);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return 0;
+}
+
+int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt, int op,
+                        unsigned flags, hipStream_t stream) {
+    size_t es;
+    if (int rc = check_dtype(dt, &es)) return rc;
+    if (int rc = check_op(op)) return rc;
+    if (int rc = check_bcast_lists(inputs, k, outs, m)) return rc;
+    if (int rc = check_bcast_args(inputs, k, outs, m, count, es)) return rc;
+    if (count == 0) return 0;
+    // one output: mi_reduce_multi, its kernels and launch plans
+    if (m == 1) return launch_reduce(inputs, k, outs[0], count, dt, op, flags, stream);
+
+    if (int rc = require_bcast_visible(inputs, k, outs, m, count * es)) return rc;
+    const Kern kern = pick(dt, op, canon_flags(dt, op, flags, k));
+    if (!kern.bcast) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
+    return issue_bcast(inputs, k, outs, m, count, es, stream, bcast_planned_waves(k, m),
+                       [&](unsigned stride_blocks, const BCArgs& a, unsigned lds) {
+                           return kern.bcast(stride_blocks, stream, a, lds);
+                       });
+}
+
+// The multiplier of mi_reduce_bcast_scaled in the compute type: float for
+// fp32, bf16 and fp16 (the conversion rounds to nearest even), double for
+// fp64.  Zero and infinity are refused after the conversion too: inf * 0 would
+// make a NaN whose bits are the multiplier's own choice.
+int check_scale(int dt, double scale, ScaleArg* sc) {
+    if (!std::isfinite(scale)) return fail(MI_E_INVALID, "scale is NaN or infinite");
+    sc->d = scale;
+    sc->f = (float)scale;
+    const bool f64 = dt == MI_FLOAT64;
+    if (f64 ? scale == 0.0 : sc->f == 0.0f)
+        return fail(MI_E_INVALID, f64 ? "scale is zero" : "scale is zero as a float (the compute type)");
+    if (!f64 && std::isinf(sc->f)) return fail(MI_E_INVALID, "scale is infinite as a float (the compute type)");
+    return 0;
+}
+
+int launch_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt,
+                               int op, unsigned flags, double scale, hipStream_t stream) {
+    size_t es;
+    if (int rc = check_dtype(dt, &es)) return rc;
+    if (int rc = check_op(op)) return rc;
+    if (op != MI_OP_SUM) return fail(MI_E_UNSUPPORTED, "op: a scaled reduction is a sum (MI_OP_SUM)");
+    if (dt != MI_FLOAT16 && dt != MI_FLOAT32 && dt != MI_FLOAT64 && dt != MI_BFLOAT16)
+        return fail(MI_E_UNSUPPORTED, "dtype: a scaled reduction needs fp16, bf16, fp32 or fp64");
+    if (int rc = check_bcast_lists(inputs, k, outs, m)) return rc;
+    ScaleArg sc;
+    if (int rc = check_scale(dt, scale, &sc)) return rc;
+    if (int rc = check_bcast_args(inputs, k, outs, m, count, es)) return rc;
+    if (count == 0) return 0;
+    if (int rc = require_bcast_visible(inputs, k, outs, m, count * es)) return rc;
+    // every (k, m), m = 1 and k = 1 included, runs the scaled fan-out kernels
+    const Kern kern = pick(dt, op, canon_flags(dt, op, flags, k));
+    if (!kern.bcast_scaled) return fail(MI_E_UNSUPPORTED, "no scaled kernel for this dtype/variant");
+    // The fan-out's residency plan, but for (2, 1): two loads and one store per
+    // lane is the 2-input reduce's stream, and wants that kernel's plan (21
+    // waves per CU), not the fan-in's for two streams (16).  At 16 the 1 GiB
+    // bf16 sum ran at 0.543 ms against 0.488 for mi_reduce_bcast (which hands
+    // m = 1 to the 2-input kernel), at 21 at 0.489; fp32 0.503 / 0.500 / 0.500
+    // (tools/scaled_sweep.py --residency, profiles/reduce_scaled/).
+    const int waves = (k == 2 && m == 1) ? planned_waves(2) : bcast_planned_waves(k, m);
+    return issue_bcast(inputs, k, outs, m, count, es, stream, waves,
+                       [&](unsigned stride_blocks, const BCArgs& a, unsigned lds) {
+                           return kern.bcast_scaled(stride_blocks, stream, a, sc, lds);
+                       });
 }
 
 // ---------------------------------------------------------------------------
@@ -2041,6 +2132,11 @@ int mi_reduce_multi(const void* const* inputs, int k, void* out, size_t count, i
 int mi_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dtype, int op,
                     unsigned flags, void* stream) {
     return launch_reduce_bcast(inputs, k, outs, m, count, dtype, op, flags, (hipStream_t)stream);
+}
+
+int mi_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dtype,
+                           int op, unsigned flags, double scale, void* stream) {
+    return launch_reduce_bcast_scaled(inputs, k, outs, m, count, dtype, op, flags, scale, (hipStream_t)stream);
 }
 
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op, unsigned flags,

@@ -282,6 +282,43 @@ __device__ __forceinline__ typename Tr<Tag>::S finish_fold(typename Tr<Tag>::C a
         return finish<Tag, V, X>(acc, idx, trunc_from);
 }
 
+// mi_reduce_bcast_scaled: the accumulator times a multiplier before its final
+// rounding.  The multiplier is a kernel argument of its own (BCArgs stays what
+// mi_reduce_bcast passes): f = (float)d is the compute type's value for fp32,
+// bf16 and fp16, d for fp64.  NoScale, the default of every fold below, is the
+// unscaled finish.
+struct NoScale {};
+struct ScaleArg {
+    double d;
+    float f;
+    template <typename C>
+    __device__ __forceinline__ C as() const {
+        if constexpr (std::is_same<C, double>::value) return d;
+        else return f;
+    }
+};
+
+// finish_fold under a multiplier: one multiply in the compute type, then the
+// variant's final conversion (finish, not finish_fold: the product of a
+// storage-precision accumulator needs its rounding).  A NaN accumulator is
+// stored as the unscaled fold stores it and never reaches the multiplier,
+// whose NaN choice is the hardware's.  X = false leaves the select out with
+// the other NaN fix-ups: a NaN accumulator makes a NaN row, and every such row
+// is refolded with X (x86_refold's screens: a sum is NaN only from a NaN or
+// Inf input, and the multiplier is finite and not zero).
+template <typename Tag, unsigned V, bool X, typename SC>
+__device__ __forceinline__ typename Tr<Tag>::S finish_scaled(typename Tr<Tag>::C acc, uint64_t idx,
+                                                             uint64_t trunc_from, const SC& sc) {
+    if constexpr (std::is_same<SC, NoScale>::value) {
+        return finish_fold<Tag, V, X>(acc, idx, trunc_from);
+    } else {
+        using C = typename Tr<Tag>::C;
+        const auto r = finish<Tag, V, X>(acc * sc.template as<C>(), idx, trunc_from);
+        if constexpr (X) return (acc != acc) ? finish_fold<Tag, V, X>(acc, idx, trunc_from) : r;
+        else return r;
+    }
+}
+
 
 // The avx512fp16 impl's VMINPH/VMAXPH(in, inout) return the selected operand
 // as stored; the fp32 route's widening (VCVTPH2PS) has quieted it.  They
@@ -361,8 +398,9 @@ __device__ __forceinline__ bool inf_nan_hit(uint32_t bits) {
     return (bits & (sizeof(typename Tr<Tag>::S) == 2 ? 0x80008000u : 0x80000000u)) != 0u;
 }
 
-template <typename Tag, int OP, unsigned V, bool X, int KMAX>
-__device__ __forceinline__ u32x4 fold_vec(const u32x4 (&x)[KMAX], int k, uint64_t e0, uint64_t trunc_from) {
+template <typename Tag, int OP, unsigned V, bool X, int KMAX, typename SC = NoScale>
+__device__ __forceinline__ u32x4 fold_vec(const u32x4 (&x)[KMAX], int k, uint64_t e0, uint64_t trunc_from,
+                                          const SC& sc = SC()) {
     using S = typename Tr<Tag>::S;
     using C = typename Tr<Tag>::C;
     constexpr int N = 16 / sizeof(S);
@@ -381,7 +419,7 @@ __device__ __forceinline__ u32x4 fold_vec(const u32x4 (&x)[KMAX], int k, uint64_
     Pack<S> pr;
 #pragma unroll
     for (int e = 0; e < N; e++) {
-        pr.e[e] = finish_fold<Tag, V, X>(acc[e], e0 + e, trunc_from);
+        pr.e[e] = finish_scaled<Tag, V, X>(acc[e], e0 + e, trunc_from, sc);
         if constexpr (X) pr.e[e] = native_minmax<Tag, OP, V>(pr.e[e], p0.e[e]);  // NaN rows take X
     }
     return __builtin_bit_cast(u32x4, pr);
@@ -394,23 +432,23 @@ __device__ __forceinline__ u32x4 fold_vec(const u32x4 (&x)[KMAX], int k, uint64_
 // screen finds every row to fix: one unordered compare per element (an
 // integer exponent screen cost C2 ~3 %, profiles/round3_run2).  Other types
 // and ops: a no-op.
-template <typename Tag, int OP, unsigned V, int KMAX>
+template <typename Tag, int OP, unsigned V, int KMAX, typename SC = NoScale>
 __device__ __forceinline__ u32x4 x86_refold(u32x4 r, const u32x4 (&x)[KMAX], int k, uint64_t e0,
-                                            uint64_t trunc_from) {
+                                            uint64_t trunc_from, const SC& sc = SC()) {
     if constexpr (Tr<Tag>::lp) {
         uint32_t bits = inf_nan_bits<Tag>(x[0]);
 #pragma unroll
         for (int i = 1; i < KMAX; i++)
             if (i < k) bits |= inf_nan_bits<Tag>(x[i]);
         if constexpr (OP == OP_PROD && KMAX > 2) bits |= inf_nan_bits<Tag>(r);
-        if (__builtin_expect(inf_nan_hit<Tag>(bits), 0)) r = fold_vec<Tag, OP, V, true, KMAX>(x, k, e0, trunc_from);
+        if (__builtin_expect(inf_nan_hit<Tag>(bits), 0)) r = fold_vec<Tag, OP, V, true, KMAX>(x, k, e0, trunc_from, sc);
     } else if constexpr (Tr<Tag>::fp && (OP == OP_SUM || OP == OP_PROD)) {
         // unordered self-compares: one v_cmp_u per element pair into a lane mask
         const Pack<Tag> p = __builtin_bit_cast(Pack<Tag>, r);
         bool nan = false;
 #pragma unroll
         for (int e = 0; e < 16 / (int)sizeof(Tag); e++) nan |= (p.e[e] != p.e[e]);
-        if (__builtin_expect(nan, 0)) r = fold_vec<Tag, OP, V, true, KMAX>(x, k, e0, trunc_from);
+        if (__builtin_expect(nan, 0)) r = fold_vec<Tag, OP, V, true, KMAX>(x, k, e0, trunc_from, sc);
     }
     return r;
 }
@@ -546,15 +584,15 @@ __device__ __forceinline__ u32x4 pk_op4(u32x4 in, u32x4 acc) {
 
 // The scalar path (head, tail, element loop): element `idx` of the fold of
 // in[0..k), as stored.
-template <typename Tag, int OP, unsigned V>
+template <typename Tag, int OP, unsigned V, typename SC = NoScale>
 __device__ __forceinline__ typename Tr<Tag>::S fold_elem(const void* const* in, int k, uint64_t idx,
-                                                         uint64_t trunc_from) {
+                                                         uint64_t trunc_from, const SC& sc = SC()) {
     using S = typename Tr<Tag>::S;
     using C = typename Tr<Tag>::C;
     const S s0 = static_cast<const S*>(in[0])[idx];
     C acc = widen<Tag>(s0);
     for (int i = 1; i < k; i++) acc = step<Tag, OP, V>(widen<Tag>(static_cast<const S*>(in[i])[idx]), acc);
-    return native_minmax<Tag, OP, V>(finish_fold<Tag, V>(acc, idx, trunc_from), s0);
+    return native_minmax<Tag, OP, V>(finish_scaled<Tag, V, true>(acc, idx, trunc_from, sc), s0);
 }
 
 template <typename Tag, int OP, unsigned V>
@@ -854,9 +892,9 @@ __global__ __launch_bounds__(B) void reduce2_batch_kernel(BArgs a) {
 // (acc = in[0]; acc = op(in[j], acc)).  Returns the lane's result vector;
 // x0 = its vector of in[0] as loaded (bcast's k = 1 rule).  `ain` is the
 // kernel argument's pointer list.
-template <typename Tag, int OP, unsigned V, int KMAX>
+template <typename Tag, int OP, unsigned V, int KMAX, typename SC = NoScale>
 __device__ __forceinline__ u32x4 fan_fold(const void* const (&ain)[kMaxInputs], int k, const Tile& t,
-                                          uint64_t head, uint64_t trunc_from, u32x4& x0) {
+                                          uint64_t head, uint64_t trunc_from, u32x4& x0, const SC& sc = SC()) {
     using S = typename Tr<Tag>::S;
     constexpr int N = 16 / sizeof(S);
     // Materialise every input pointer before the first branch: left alone, the
@@ -900,8 +938,8 @@ __device__ __forceinline__ u32x4 fan_fold(const void* const (&ain)[kMaxInputs], 
         Pack<S> pr;
         const uint64_t e0 = head + (t.t0 + threadIdx.x) * N;
 #pragma unroll
-        for (int e = 0; e < N; e++) pr.e[e] = finish_fold<Tag, V, false>(acc[e], e0 + e, trunc_from);
-        return x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, trunc_from);
+        for (int e = 0; e < N; e++) pr.e[e] = finish_scaled<Tag, V, false>(acc[e], e0 + e, trunc_from, sc);
+        return x86_refold<Tag, OP, V, KMAX>(__builtin_bit_cast(u32x4, pr), x, k, e0, trunc_from, sc);
     }
 }
 
@@ -971,6 +1009,11 @@ __global__ __launch_bounds__(B) void fan_kernel(KArgs a) {
 // has the outputs' misalignment, so a lane loads exactly the bytes it later
 // stores, and every lane has all k loads back (the refold keeps them in
 // registers: no re-load) before its first store.
+//   mi_reduce_bcast_scaled runs the same bodies with a multiplier in the
+// finish step (finish_scaled), selected at compile time by the SC parameter:
+// kernels of their own, sum on the floating types only, for every (k, m).
+// The multiply sits after the last combine, so the order of loads and stores,
+// and with it the in-place argument above, is unchanged.
 // ---------------------------------------------------------------------------
 struct BCArgs {
     const void* in[kMaxInputs];  // in[0] = accumulator start
@@ -993,11 +1036,40 @@ constexpr bool bcast_copies_k1() {
     return Tr<Tag>::lp && !(V & V_ACC_FP32);
 }
 
-template <typename Tag, int OP, unsigned V>
-__device__ __forceinline__ void bcast_elem(const BCArgs& a, int k, int m, uint64_t idx) {
+// The k = 1 rule on a lane's result vector `r`, x0 = its vector of in[0] as
+// loaded.  Unscaled: x0.  Scaled: the unscaled store is in[0]'s bytes, so a
+// NaN goes out as loaded (the rounding in `r` has quieted a signalling fp16
+// NaN); every other element is the scaled one.
+template <typename Tag, typename SC>
+__device__ __forceinline__ u32x4 bcast_k1(u32x4 r, u32x4 x0) {
+    if constexpr (std::is_same<SC, NoScale>::value) {
+        return x0;
+    } else {
+        using S = typename Tr<Tag>::S;
+        Pack<S> pr = __builtin_bit_cast(Pack<S>, r);
+        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x0);
+#pragma unroll
+        for (int e = 0; e < 16 / (int)sizeof(S); e++) {
+            const typename Tr<Tag>::C w = widen<Tag>(p0.e[e]);
+            pr.e[e] = (w != w) ? p0.e[e] : pr.e[e];
+        }
+        return __builtin_bit_cast(u32x4, pr);
+    }
+}
+
+template <typename Tag, int OP, unsigned V, typename SC = NoScale>
+__device__ __forceinline__ void bcast_elem(const BCArgs& a, int k, int m, uint64_t idx, const SC& sc = SC()) {
     using S = typename Tr<Tag>::S;
-    S r = fold_elem<Tag, OP, V>(a.in, k, idx, a.trunc_from);
-    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? static_cast<const S*>(a.in[0])[idx] : r;
+    S r = fold_elem<Tag, OP, V>(a.in, k, idx, a.trunc_from, sc);
+    if constexpr (bcast_copies_k1<Tag, V>()) {
+        if constexpr (std::is_same<SC, NoScale>::value) {
+            r = (k == 1) ? static_cast<const S*>(a.in[0])[idx] : r;
+        } else if (k == 1) {  // bcast_k1's rule
+            const S s0 = static_cast<const S*>(a.in[0])[idx];
+            const typename Tr<Tag>::C w = widen<Tag>(s0);
+            r = (w != w) ? s0 : r;
+        }
+    }
     for (int o = 0; o < m; o++) static_cast<S*>(a.out[o])[idx] = r;
 }
 
@@ -1017,18 +1089,30 @@ __device__ __forceinline__ void bcast_store(const BCArgs& a, int m, u32x4 r, con
 }
 
 // One tile of B vectors per block: fan_fold (all k loads before the first
-// combine), then the m stores.
-template <typename Tag, int OP, unsigned V, int B, int KMAX>
-__global__ __launch_bounds__(B) void bcast_kernel(BCArgs a) {
+// combine), then the m stores.  bcast_kernel and bcast_scaled_kernel are this
+// body without and with a multiplier.
+template <typename Tag, int OP, unsigned V, int B, int KMAX, typename SC>
+__device__ __forceinline__ void bcast_tile(const BCArgs& a, const SC& sc) {
     constexpr int N = 16 / sizeof(typename Tr<Tag>::S);
     const int k = a.k, m = a.m;
-    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N, [&](uint64_t i) { bcast_elem<Tag, OP, V>(a, k, m, i); });
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N,
+              [&](uint64_t i) { bcast_elem<Tag, OP, V>(a, k, m, i, sc); });
     const Tile t = tile_of<B>(blockIdx.x, a.nvec, a.head * sizeof(typename Tr<Tag>::S));
     if (t.t0 >= a.nvec) return;
     u32x4 x0;
-    u32x4 r = fan_fold<Tag, OP, V, KMAX>(a.in, k, t, a.head, a.trunc_from, x0);
-    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x0 : r;
+    u32x4 r = fan_fold<Tag, OP, V, KMAX>(a.in, k, t, a.head, a.trunc_from, x0, sc);
+    if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? bcast_k1<Tag, SC>(r, x0) : r;
     bcast_store(a, m, r, t);
+}
+
+template <typename Tag, int OP, unsigned V, int B, int KMAX>
+__global__ __launch_bounds__(B) void bcast_kernel(BCArgs a) {
+    bcast_tile<Tag, OP, V, B, KMAX>(a, NoScale());
+}
+
+template <typename Tag, int OP, unsigned V, int B, int KMAX>
+__global__ __launch_bounds__(B) void bcast_scaled_kernel(BCArgs a, ScaleArg sc) {
+    bcast_tile<Tag, OP, V, B, KMAX>(a, sc);
 }
 
 // The grid-stride form, for launches under mi_set_max_blocks and for the
@@ -1085,6 +1169,53 @@ __global__ __launch_bounds__(B) void bcast_stride_kernel(BCArgs a) {
             r = __builtin_bit_cast(u32x4, pr);
             if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? x0 : r;
         }
+        bcast_store(a, m, r, t);
+    }
+}
+
+// bcast_stride_kernel under a multiplier, for a floating type.  A kernel text
+// of its own: with one body shared through a callee, bcast_stride_kernel's
+// registers moved (its arguments by reference: the fp16 min / max forms with
+// fp32 accumulation 21 -> 23 and 30 -> 32 VGPRs; by value: most forms, either
+// way).
+template <typename Tag, int OP, unsigned V, int B>
+__global__ __launch_bounds__(B) void bcast_scaled_stride_kernel(BCArgs a, ScaleArg sc) {
+    using S = typename Tr<Tag>::S;
+    constexpr int N = 16 / sizeof(S);
+    const int k = a.k, m = a.m;
+    if (a.scalar_only) {
+        for (uint64_t i = (uint64_t)blockIdx.x * B + threadIdx.x; i < a.count; i += (uint64_t)gridDim.x * B)
+            bcast_elem<Tag, OP, V>(a, k, m, i, sc);
+        return;
+    }
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.nvec * N,
+              [&](uint64_t i) { bcast_elem<Tag, OP, V>(a, k, m, i, sc); });
+    for (uint64_t tile = blockIdx.x; tile * B < a.nvec; tile += gridDim.x) {
+        const Tile t = tile_of<B>(tile, a.nvec, a.head * sizeof(S));
+        const auto load = [&](int i) {
+            return __builtin_amdgcn_raw_buffer_load_b128(tile_rsrc(a.in[i], t.byte0, t.bytes), t.off, 0, kAuxNT);
+        };
+        const u32x4 x0 = load(0);
+        u32x4 cur = x0;
+        if (k >= 2) cur = load(1);
+        typename Tr<Tag>::C acc[N];
+        const Pack<S> p0 = __builtin_bit_cast(Pack<S>, x0);
+#pragma unroll
+        for (int e = 0; e < N; e++) acc[e] = widen<Tag>(p0.e[e]);
+        for (int i = 1; i < k; i++) {
+            u32x4 nxt = cur;
+            if (i + 1 < k) nxt = load(i + 1);
+            const Pack<S> pi = __builtin_bit_cast(Pack<S>, cur);
+#pragma unroll
+            for (int e = 0; e < N; e++) acc[e] = step<Tag, OP, V>(widen<Tag>(pi.e[e]), acc[e]);
+            cur = nxt;
+        }
+        Pack<S> pr;
+        const uint64_t e0 = a.head + (t.t0 + threadIdx.x) * N;
+#pragma unroll
+        for (int e = 0; e < N; e++) pr.e[e] = finish_scaled<Tag, V, true>(acc[e], e0 + e, a.trunc_from, sc);
+        u32x4 r = __builtin_bit_cast(u32x4, pr);
+        if constexpr (bcast_copies_k1<Tag, V>()) r = (k == 1) ? bcast_k1<Tag, ScaleArg>(r, x0) : r;
         bcast_store(a, m, r, t);
     }
 }
