@@ -77,7 +77,9 @@ enum mi_dtype {
 /* Low-precision (bf16/fp16) fan-in accumulates in fp32 and rounds once at
  * the end: ccl_comp_batch_reduce(..., bf16_keep_precision_mode=1, ...),
  * src/comp/comp.cpp:214-234.  Clear = round to storage after every
- * pairwise step (chained ccl_comp_reduce, comp.cpp:236-245).               */
+ * pairwise step (chained ccl_comp_reduce, comp.cpp:236-245).  One input
+ * (k = 1) still runs the two conversions: a signalling fp16 NaN comes out
+ * quiet (VCVTPH2PS), where without the flag k = 1 copies the bytes.         */
 #define MI_F_ACC_FP32 0x4u
 /* With MI_F_ACC_FP32|MI_F_BF16_RNE: the last (count % 16) elements of the
  * final fp32 -> bf16 conversion are truncated, as the scalar tail loop of

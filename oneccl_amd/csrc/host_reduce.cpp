@@ -479,7 +479,8 @@ unsigned canon(int dt, int op, unsigned f, int k) {
         case MI_FLOAT64: return mm ? (f & MI_F_MINMAX_INOUT_FIRST) : 0u;
         case MI_FLOAT16: {
             unsigned v = (mm ? (f & (MI_F_MINMAX_INOUT_FIRST | MI_F_FP16_NATIVE_MINMAX)) : 0u) | (f & MI_F_ACC_FP32);
-            if (k <= 1 || (k == 2 && mm)) v &= ~MI_F_ACC_FP32;  // a sum/prod step keeps its NaN order
+            // a sum/prod step keeps its NaN order; k = 1 its widening, which quiets a signalling NaN
+            if (k == 2 && mm) v &= ~MI_F_ACC_FP32;
             return v;
         }
         case MI_BFLOAT16: {

@@ -141,9 +141,11 @@ unsigned canon_flags(int dt, int op, unsigned f, int k) {
             unsigned v = (mm ? (f & (V_INOUT_FIRST | V_FP16_NATIVE)) : 0u) | (f & V_ACC_FP32);
             // One step rounds once either way, but a sum/prod step with fp32
             // accumulation takes the accumulator's NaN first (CCL_REDUCE(float)
-            // order), a storage-precision step `in`'s: only min/max (and k = 1,
-            // no step) may drop the bit.
-            if (k <= 1 || (k == 2 && mm)) v &= ~V_ACC_FP32;
+            // order), a storage-precision step `in`'s: only min/max may drop the
+            // bit.  k = 1 keeps it: no step runs, but the widening to the fp32
+            // accumulator (VCVTPH2PS) quiets a signalling NaN, which a copy of
+            // the bytes would leave signalling.
+            if (k == 2 && mm) v &= ~V_ACC_FP32;
             return v;
         }
         case MI_BFLOAT16: {

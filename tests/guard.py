@@ -104,15 +104,16 @@ def tile_shapes(es, T):
     return out + [(1, es % 16)]
 
 
-def oracle_fold(ins, dt, op, flags):
+def oracle_fold(ins, dt, op, flags, fp16_impl=oracle.FP16_AVX512F):
     """The oracle's left fold of `ins` under the semantic variant `flags`
-    (include/mi_reduce.h) selects."""
+    (include/mi_reduce.h) selects.  fp16_impl = oracle.FP16_AVX512FP16 is
+    MI_F_FP16_NATIVE_MINMAX's min / max in storage precision."""
     if flags & F_ACC_FP32:
         return oracle.lp_fanin_acc_fp32(ins, dt, op, dt == FP16 or bool(flags & F_BF16_RNE),
                                         bool(flags & F_MINMAX_INOUT_FIRST))
     bimpl = oracle.BF16_AVX512BF if flags & F_BF16_RNE else (
         oracle.BF16_AVX512F if flags & F_MINMAX_INOUT_FIRST else oracle.BF16_SCALAR)
-    return oracle.fanin(ins, dt, op, bimpl, oracle.FP16_AVX512F)
+    return oracle.fanin(ins, dt, op, bimpl, fp16_impl)
 
 
 def _bits(a):
