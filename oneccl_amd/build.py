@@ -47,7 +47,8 @@ def _run(cmd: list[str]) -> None:
 
 def build_mi_reduce(force: bool = False) -> Path:
     out = LIB / "libmi_reduce.so"
-    deps = [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", CSRC / "vec_grid.hpp", ROOT / "include" / "mi_reduce.h"]
+    deps = [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", CSRC / "vec_grid.hpp", CSRC / "host_span.hpp",
+            ROOT / "include" / "mi_reduce.h"]
     if force or _stale(out, deps):
         LIB.mkdir(exist_ok=True)
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall",
@@ -222,7 +223,8 @@ def build_asan(force: bool = False) -> Path:
     adir.mkdir(parents=True, exist_ok=True)
     san = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fno-omit-frame-pointer"]
     mi = adir / "libmi_reduce.so"
-    if force or _stale(mi, [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", CSRC / "vec_grid.hpp"]):
+    if force or _stale(mi, [CSRC / "mi_reduce.hip", CSRC / "reduce_kernels.hpp", CSRC / "vec_grid.hpp",
+                            CSRC / "host_span.hpp"]):
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", *san,
               "-o", str(mi), str(CSRC / "mi_reduce.hip")])
     shim = adir / "libccl_comp_hip.so"

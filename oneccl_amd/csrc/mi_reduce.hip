@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/mi_reduce.h"
+#include "host_span.hpp"
 #include "reduce_kernels.hpp"
 #include "vec_grid.hpp"
 
@@ -999,8 +1000,6 @@ int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsign
 // ---------------------------------------------------------------------------
 // per-thread device context: stream + scratch for host-operand staging
 // ---------------------------------------------------------------------------
-constexpr size_t kChunkBytes = 32ull << 20;  // staging chunk per operand
-
 struct DevCtx {
     int device = -1;
     hipStream_t stream[2] = {nullptr, nullptr};
@@ -1009,7 +1008,6 @@ struct DevCtx {
     hipStream_t d2h = nullptr;              // the drain thread's stream (created on first use)
     hipEvent_t ready[2] = {nullptr, nullptr};  // per slot: the chunk's result is in dbuf
     std::vector<void*> hbuf;                // pinned bounce buffers for small pageable operands
-    size_t hbuf_bytes = 0;
     char* edge = nullptr;                   // pinned scratch for the unaligned ends of D2H copies (Edges)
 
     ~DevCtx() {
@@ -1054,10 +1052,7 @@ struct HostCopy {
 //    (< 16 bytes each) go to pinned scratch and are copied to the destination
 //    by the CPU after the stream is done (Edges, d2h_pageable).  Nothing
 //    outside the destination is written.
-constexpr uintptr_t kHostAlign = 16;
-constexpr size_t kStageSlack = 2 * kHostAlign;  // a staging buffer holds a chunk and its alignment
-inline uintptr_t host_align_dn(uintptr_t a) { return a & ~(kHostAlign - 1); }
-inline uintptr_t host_align_up(uintptr_t a) { return (a + kHostAlign - 1) & ~(kHostAlign - 1); }
+// The spans themselves are host_span.hpp's: host_hull, host_split.
 
 // Test hook (mi_test_fail_copy): the nth staged host copy from now on fails
 // with hipErrorInvalidValue before it reaches the runtime (no sticky state).
@@ -1083,14 +1078,13 @@ const char* kind_name(PtrKind k) { return k == PK_DEVICE ? "device" : k == PK_PI
 // aligned interior (d2h_pageable, mi_copy_sync's H2D).
 std::string copy_geometry(const void* host, size_t bytes, size_t chunk, PtrKind kind, bool hull) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(host);
-    const uintptr_t lo = hull ? host_align_dn(a) : std::min(host_align_up(a), a + bytes);
-    const uintptr_t hi = hull ? host_align_up(a + bytes) : std::max(lo, host_align_dn(a + bytes));
+    const HostSpan rt = runtime_span(a, bytes, hull);
     char buf[320];
     snprintf(buf, sizeof buf,
              " [%s host operand: addr & 4095 = %zu, %zu bytes, ends at page offset %zu; runtime span: addr & 4095 "
              "= %zu, %zu bytes; chunk %zu]",
-             kind_name(kind), (size_t)(a & 4095), bytes, (size_t)((a + bytes) & 4095), (size_t)(lo & 4095),
-             (size_t)(hi - lo), chunk);
+             kind_name(kind), (size_t)(a & 4095), bytes, (size_t)((a + bytes) & 4095), (size_t)(rt.lo & 4095),
+             rt.bytes, chunk);
     return buf;
 }
 
@@ -1100,22 +1094,26 @@ int copy_fail(hipError_t e, const char* what, const void* host, size_t bytes, si
     return (int)e;
 }
 
-hipError_t h2d_stage(void* dst, const void* src, size_t bytes, hipStream_t s, size_t* shift) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    const uintptr_t lo = host_align_dn(a), hi = host_align_up(a + bytes);
-    *shift = a - lo;
+// H2D of the hull of host [src, src + bytes) to device `dst`: the operand then
+// starts host_hull(src, bytes).shift bytes into dst.
+hipError_t h2d_stage(void* dst, const void* src, size_t bytes, hipStream_t s) {
+    const HostHull h = host_hull(reinterpret_cast<uintptr_t>(src), bytes);
     if (injected_copy_failure()) return hipErrorInvalidValue;
-    return hipMemcpyAsync(dst, reinterpret_cast<const void*>(lo), hi - lo, hipMemcpyHostToDevice, s);
+    return hipMemcpyAsync(dst, reinterpret_cast<const void*>(h.lo), h.hi - h.lo, hipMemcpyHostToDevice, s);
 }
 
-constexpr size_t kEdgeBytes = 8192;            // DevCtx::edge
-constexpr size_t kEdgeSlot = 2 * kHostAlign;   // one D2H: head + tail
+constexpr size_t kEdgeBytes = 8192;                    // DevCtx::edge: slots of kEdgeSlot bytes
 constexpr size_t kDrainEdge = kEdgeBytes - kEdgeSlot;  // the drain thread's slot (the last one)
 
 struct Edges {
-    char* pin = nullptr;  // pinned scratch, kEdgeSlot bytes per D2H
+    char* pin = nullptr;  // pinned scratch, kEdgeSlot bytes per copy
     size_t slots = 0, used = 0;
     std::vector<HostCopy> post;
+    // `n` slots of pinned scratch from `p` on
+    void open(char* p, size_t n) {
+        pin = p;
+        slots = n;
+    }
     bool full() const { return used >= slots; }
     // after the stream(s) carrying the D2H copies are done
     void flush() {
@@ -1137,10 +1135,7 @@ int ensure_edges(DevCtx* d) {
 // D2H of device [src, src + bytes) into pageable host memory at dst; needs a
 // free slot in `e` (the caller flushes a full one first).
 hipError_t d2h_pageable(void* dst, const void* src, size_t bytes, hipStream_t s, Edges& e) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(dst);
-    const size_t head = std::min(bytes, (size_t)(host_align_up(a) - a));
-    const size_t interior = (bytes - head) & ~(size_t)(kHostAlign - 1);
-    const size_t tail = bytes - head - interior;
+    const auto [head, interior, tail] = host_split(reinterpret_cast<uintptr_t>(dst), bytes);
     const char* s8 = static_cast<const char*>(src);
     char* d8 = static_cast<char*>(dst);
     if (injected_copy_failure()) return hipErrorInvalidValue;
@@ -1153,11 +1148,33 @@ hipError_t d2h_pageable(void* dst, const void* src, size_t bytes, hipStream_t s,
             e.post.push_back(HostCopy{d8, slot, head});
         }
         if (r == hipSuccess && tail) {
-            r = hipMemcpyAsync(slot + kHostAlign, s8 + head + interior, tail, hipMemcpyDeviceToHost, s);
-            e.post.push_back(HostCopy{d8 + head + interior, slot + kHostAlign, tail});
+            r = hipMemcpyAsync(slot + kEdgeTail, s8 + head + interior, tail, hipMemcpyDeviceToHost, s);
+            e.post.push_back(HostCopy{d8 + head + interior, slot + kEdgeTail, tail});
         }
     }
     return r;
+}
+
+// Its mirror, for mi_copy_sync: H2D of pageable host [src, src + bytes) to
+// device `dst`.  The CPU copies the ends into the first slot of `edges`
+// (opened by the caller, who waits for `st` before using it again); the
+// interior goes direct, and only its failure carries the copy's geometry.
+int h2d_pageable(void* dst, const void* src, size_t bytes, hipStream_t st, Edges& edges) {
+    const auto [head, interior, tail] = host_split(reinterpret_cast<uintptr_t>(src), bytes);
+    const char* s8 = static_cast<const char*>(src);
+    char* d8 = static_cast<char*>(dst);
+    if (head) {
+        memcpy(edges.pin, s8, head);
+        MI_HIP(hipMemcpyAsync(d8, edges.pin, head, hipMemcpyHostToDevice, st));
+    }
+    if (interior)
+        if (hipError_t he = hipMemcpyAsync(d8 + head, s8 + head, interior, hipMemcpyHostToDevice, st))
+            return copy_fail(he, "H2D copy (mi_copy_sync)", src, bytes, 0, PK_PAGEABLE, false);
+    if (tail) {
+        memcpy(edges.pin + kEdgeTail, s8 + head + interior, tail);
+        MI_HIP(hipMemcpyAsync(d8 + head + interior, edges.pin + kEdgeTail, tail, hipMemcpyHostToDevice, st));
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1258,8 +1275,7 @@ struct Drain {
         helper_thread_affinity();
         hipError_t e = hipSetDevice(device);
         Edges ed;
-        ed.pin = edge;
-        ed.slots = 1;
+        ed.open(edge, 1);
         for (;;) {
             Task t;
             {
@@ -1469,7 +1485,6 @@ int ensure_bounce(DevCtx* d, size_t nbuf) {
         MI_HIP(hipHostMalloc(&p, kBounceBytes, hipHostMallocDefault));
         d->hbuf.push_back(p);
     }
-    d->hbuf_bytes = kBounceBytes;
     return 0;
 }
 
@@ -1494,6 +1509,130 @@ int ensure_scratch(DevCtx* d, size_t nbuf, size_t bytes) {
         }
     }
     d->dbuf_bytes = want;
+    return 0;
+}
+
+// ---- the staged pipeline ---------------------------------------------------
+// One operand of a staged call: the pointer as the caller gave it, its class
+// and its element size.
+struct StagedOp {
+    const void* ptr;
+    PtrKind kind;
+    size_t es;
+};
+
+// An element-wise call over `count` elements whose host operands go through
+// device staging buffers: ops[0 .. k) are read, ops[k] is written.  Chunks of
+// stage_chunk_elems elements, two pipeline slots on two streams (the H2D of
+// chunk c + 1 overlaps the kernel / D2H of chunk c).  Per chunk: the H2D of
+// every distinct host input in operand order (h2d_stage); then
+// launch(elem_offset, n, ins, out, stream) on the chunk's device addresses;
+// then the D2H of a host output -- handed to the drain thread (pageable, more
+// than one chunk, a `drain` given), through d2h_pageable and the Edges
+// (pageable), or as one copy of the exact span (pinned).  `what` ends the
+// copies' error prefixes.
+// Waits for the streams only to flush full Edges: *used = the streams that
+// carry work (bit 0: stream[0], bit 1: stream[1]).  The ends still in pinned
+// scratch at the end go to `post`, for the caller to copy after its wait;
+// without one they are waited for and copied here.
+template <class Launch>
+int staged_pipeline(DevCtx* d, const StagedOp* ops, int k, size_t count, const char* what, const Launch& launch,
+                    int* used, Drain* drain, std::vector<HostCopy>* post) {
+    // distinct host operands get a device staging buffer per slot; the output
+    // reuses the buffer of the input it aliases (in-place inout; never across
+    // element sizes: a conversion keeps a buffer per side)
+    int slot_of[MI_MAX_INPUTS + 1];
+    int nhost = 0;
+    size_t es_max = 0;
+    for (int i = 0; i <= k; i++) {
+        es_max = std::max(es_max, ops[i].es);
+        slot_of[i] = -1;
+        if (ops[i].kind == PK_DEVICE) continue;
+        for (int j = 0; j < i; j++)
+            if (slot_of[j] >= 0 && ops[j].ptr == ops[i].ptr && ops[j].es == ops[i].es) slot_of[i] = slot_of[j];
+        if (slot_of[i] < 0) slot_of[i] = nhost++;
+    }
+    const size_t chunk_elems = stage_chunk_elems(es_max);
+    int rc = ensure_scratch(d, (size_t)nhost, stage_buf_bytes(es_max));
+    if (rc) return rc;
+
+    const size_t nchunks = (count + chunk_elems - 1) / chunk_elems;
+    *used = nchunks > 1 ? 3 : 1;
+    const StagedOp& o = ops[k];
+    const bool d2h_pg = o.kind == PK_PAGEABLE;
+    const bool drained = drain && d2h_pg && nchunks > 1;
+    Edges edges;  // unaligned ends of the D2H copies this thread issues
+    if (d2h_pg) {
+        rc = ensure_edges(d);
+        if (rc) return rc;
+        edges.open(d->edge, kDrainEdge / kEdgeSlot);
+    }
+    if (drained) {
+        if (!d->d2h) MI_HIP(hipStreamCreateWithFlags(&d->d2h, hipStreamNonBlocking));
+        for (int s = 0; s < 2; s++)
+            if (!d->ready[s]) MI_HIP(hipEventCreateWithFlags(&d->ready[s], hipEventDisableTiming));
+        drain->start(d->device, d->d2h, d->edge + kDrainEdge);
+    }
+    auto failed = [&](hipError_t he, const char* copy, const void* host, size_t bytes, size_t c, PtrKind kind,
+                      bool hull) {
+        return copy_fail(he, (std::string(copy) + what).c_str(), host, bytes, c, kind, hull);
+    };
+    auto wait_and_flush = [&]() -> int {
+        for (int q = 0; q < 2; q++) MI_HIP(wait_stream(d->stream[q]));
+        edges.flush();
+        return 0;
+    };
+    for (size_t c = 0; c < nchunks; c++) {
+        const int s = (int)(c & 1);
+        hipStream_t st = d->stream[s];
+        // slot s holds chunk c-2's result until the helper has copied it out
+        if (drained && c >= 2)
+            if (hipError_t he = drain->wait_done(c - 1)) {
+                hip_fail(he, "staged D2H into pageable memory (drain thread)");
+                g_last_error += drain->err_where;
+                return (int)he;
+            }
+        const size_t off = c * chunk_elems;
+        const size_t n = std::min(chunk_elems, count - off);
+        // each operand's chunk: on the host, and where the kernel finds it --
+        // a host operand at its hull's shift in its staging buffer
+        const void* host[MI_MAX_INPUTS + 1];
+        const void* dev[MI_MAX_INPUTS + 1];
+        unsigned loaded = 0;
+        for (int i = 0; i <= k; i++) {
+            host[i] = dev[i] = static_cast<const char*>(ops[i].ptr) + off * ops[i].es;
+            if (slot_of[i] < 0) continue;
+            char* buf = static_cast<char*>(d->dbuf[s][slot_of[i]]);
+            const size_t bytes = n * ops[i].es;
+            if (i < k && !(loaded >> slot_of[i] & 1)) {
+                if (hipError_t he = h2d_stage(buf, host[i], bytes, st))
+                    return failed(he, "H2D staging copy", host[i], bytes, c, ops[i].kind, true);
+                loaded |= 1u << slot_of[i];
+            }
+            dev[i] = buf + host_hull(reinterpret_cast<uintptr_t>(host[i]), bytes).shift;
+        }
+        void* cdst = const_cast<void*>(dev[k]);
+        rc = launch(off, n, dev, cdst, st);
+        if (rc) return rc;
+        if (slot_of[k] >= 0) {
+            void* hdst = const_cast<void*>(host[k]);
+            const size_t bytes = n * o.es;
+            if (drained) {
+                MI_HIP(hipEventRecord(d->ready[s], st));
+                drain->push({hdst, cdst, bytes, d->ready[s], c});
+            } else if (d2h_pg) {
+                if (edges.full())  // every slot holds an end not yet copied out
+                    if ((rc = wait_and_flush())) return rc;
+                if (hipError_t he = d2h_pageable(hdst, cdst, bytes, st, edges))
+                    return failed(he, "D2H result copy", hdst, bytes, c, o.kind, false);
+            } else if (hipError_t he = hipMemcpyAsync(hdst, cdst, bytes, hipMemcpyDeviceToHost, st)) {
+                return failed(he, "D2H result copy", hdst, bytes, c, o.kind, true);
+            }
+        }
+    }
+    if (edges.post.empty()) return 0;
+    if (!post) return wait_and_flush();
+    post->insert(post->end(), edges.post.begin(), edges.post.end());  // copied by the caller after its wait
     return 0;
 }
 
@@ -1527,8 +1666,8 @@ void classify_all(const void* const* inputs, int k, void* out, size_t bytes, Kin
 // Issue a fold with any pointer kinds on the calling thread's streams of the
 // chosen device; *used = the streams that carry work (bit 0: stream[0],
 // bit 1: stream[1]).  All-device or zero-copy: one launch on stream[0].
-// Otherwise: chunks of kChunkBytes, two pipeline slots on two streams (H2D
-// of chunk c+1 overlaps the kernel / D2H of chunk c).
+// Small pageable operands of a synchronous caller: bounce buffers.
+// Otherwise: staged_pipeline.
 int reduce_issue(const void* const* inputs, int k, void* out, size_t count, int dt, int op,
                  unsigned flags, int device, DevCtx** ctx, int* used, Drain* drain = nullptr,
                  std::vector<HostCopy>* post = nullptr, hipEvent_t* t_start = nullptr,
@@ -1619,114 +1758,17 @@ int reduce_issue(const void* const* inputs, int k, void* out, size_t count, int 
         return 0;
     }
 
-    // distinct host operands get a device staging buffer per slot; `out`
-    // reuses the buffer of the input it aliases (in-place inout)
-    int slot_of[MI_MAX_INPUTS + 1];
-    const void* host_ptr[MI_MAX_INPUTS + 1];
-    int nhost = 0;
-    for (int i = 0; i <= k; i++) {
-        const void* p = (i < k) ? inputs[i] : out;
-        const PtrKind kk = (i < k) ? kin[i] : kout;
-        slot_of[i] = -1;
-        if (kk == PK_DEVICE) continue;
-        for (int j = 0; j < nhost; j++)
-            if (host_ptr[j] == p) slot_of[i] = j;
-        if (slot_of[i] < 0) {
-            host_ptr[nhost] = p;
-            slot_of[i] = nhost++;
-        }
-    }
-    size_t chunk_elems = kChunkBytes / es;
-    chunk_elems -= chunk_elems % 16;  // keeps VCVTNEPS2BF16-tail split aligned (see below)
-    // each host operand sits at its own 16-byte offset in its staging buffers
-    // (h2d_stage); chunk starts are 16-byte multiples apart, so every chunk
-    // keeps it
-    size_t shift[MI_MAX_INPUTS + 1];
-    for (int j = 0; j < nhost; j++) shift[j] = reinterpret_cast<uintptr_t>(host_ptr[j]) & (kHostAlign - 1);
-    rc = ensure_scratch(d, (size_t)nhost, chunk_elems * es + kStageSlack);
-    if (rc) return rc;
-
-    const size_t nchunks = (count + chunk_elems - 1) / chunk_elems;
-    *used = nchunks > 1 ? 3 : 1;
-    const bool d2h_pg = kout == PK_PAGEABLE && slot_of[k] >= 0;
-    const bool drained = drain && d2h_pg && nchunks > 1;
-    Edges edges;  // unaligned ends of the D2H copies this thread issues
-    if (d2h_pg) {
-        rc = ensure_edges(d);
-        if (rc) return rc;
-        edges.pin = d->edge;
-        edges.slots = kDrainEdge / kEdgeSlot;
-    }
-    if (drained) {
-        if (!d->d2h) MI_HIP(hipStreamCreateWithFlags(&d->d2h, hipStreamNonBlocking));
-        for (int s = 0; s < 2; s++)
-            if (!d->ready[s]) MI_HIP(hipEventCreateWithFlags(&d->ready[s], hipEventDisableTiming));
-        drain->start(d->device, d->d2h, d->edge + kDrainEdge);
-    }
-    for (size_t c = 0; c < nchunks; c++) {
-        const int s = (int)(c & 1);
-        hipStream_t st = d->stream[s];
-        // slot s holds chunk c-2's result until the helper has copied it out
-        if (drained && c >= 2)
-            if (hipError_t he = drain->wait_done(c - 1)) {
-                hip_fail(he, "staged D2H into pageable memory (drain thread)");
-                g_last_error += drain->err_where;
-                return (int)he;
-            }
-        const size_t off = c * chunk_elems;
-        const size_t n = std::min(chunk_elems, count - off);
-        const size_t bytes = n * es;
-        const void* din[MI_MAX_INPUTS];
-        std::vector<bool> loaded((size_t)nhost, false);
-        for (int i = 0; i < k; i++) {
-            if (slot_of[i] < 0) {
-                din[i] = static_cast<const char*>(inputs[i]) + off * es;
-            } else {
-                char* buf = static_cast<char*>(d->dbuf[s][slot_of[i]]);
-                if (!loaded[slot_of[i]]) {
-                    size_t sh = 0;
-                    const void* hsrc = static_cast<const char*>(inputs[i]) + off * es;
-                    if (hipError_t he = h2d_stage(buf, hsrc, bytes, st, &sh))
-                        return copy_fail(he, "H2D staging copy", hsrc, bytes, c, kin[i], true);
-                    loaded[slot_of[i]] = true;
-                }
-                din[i] = buf + shift[slot_of[i]];
-            }
-        }
-        void* cdst = (slot_of[k] < 0) ? static_cast<char*>(out) + off * es
-                                      : static_cast<char*>(d->dbuf[s][slot_of[k]]) + shift[slot_of[k]];
-        // The tail-truncation split is defined on the whole array: only the
-        // last chunk holds elements >= (count/16)*16, and chunk starts are
-        // multiples of 16, so the per-chunk split computed inside
-        // launch_reduce is the same split.
-        rc = launch_reduce(din, k, cdst, n, dt, op, flags, st, true);
-        if (rc) return rc;
-        if (slot_of[k] >= 0) {
-            void* hdst = static_cast<char*>(out) + off * es;
-            if (drained) {
-                MI_HIP(hipEventRecord(d->ready[s], st));
-                drain->push({hdst, cdst, bytes, d->ready[s], c});
-            } else if (d2h_pg) {
-                if (edges.full()) {  // every slot holds an end not yet copied out
-                    for (int q = 0; q < 2; q++) MI_HIP(wait_stream(d->stream[q]));
-                    edges.flush();
-                }
-                if (hipError_t he = d2h_pageable(hdst, cdst, bytes, st, edges))
-                    return copy_fail(he, "D2H result copy", hdst, bytes, c, kout, false);
-            } else if (hipError_t he = hipMemcpyAsync(hdst, cdst, bytes, hipMemcpyDeviceToHost, st)) {
-                return copy_fail(he, "D2H result copy", hdst, bytes, c, kout, true);
-            }
-        }
-    }
-    if (!edges.post.empty()) {
-        if (post) {  // copied by the synchronous caller after its wait
-            post->insert(post->end(), edges.post.begin(), edges.post.end());
-        } else {
-            for (int q = 0; q < 2; q++) MI_HIP(wait_stream(d->stream[q]));
-            edges.flush();
-        }
-    }
-    return 0;
+    // Staged.  The tail-truncation split is defined on the whole array; the
+    // split launch_reduce computes per chunk is the same one (stage_chunk_elems).
+    StagedOp ops[MI_MAX_INPUTS + 1];
+    for (int i = 0; i < k; i++) ops[i] = {inputs[i], kin[i], es};
+    ops[k] = {out, kout, es};
+    return staged_pipeline(
+        d, ops, k, count, "",
+        [&](size_t, size_t n, const void* const* din, void* cdst, hipStream_t st) {
+            return launch_reduce(din, k, cdst, n, dt, op, flags, st, true);
+        },
+        used, drain, post);
 }
 
 int reduce_sync(const void* const* inputs, int k, void* out, size_t count, int dt, int op,
@@ -1800,11 +1842,47 @@ struct AsyncJob {
     }
 };
 
-int run_split(AsyncJob& j);
-int split_job(AsyncJob& j) { return run_split(j); }
-
 double mono_s() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// A split job, on the staging worker: the GPU part is started from here (a
+// pageable one is staged by this thread's own worker, one level down), the
+// head is folded on this thread meanwhile, then the GPU part is waited for.
+// The head runs in ~8 MiB chunks (multiples of 256 elements, so none holds a
+// keep-precision truncated tail), polling the GPU part between them: both
+// parts' durations are known even when the GPU finishes first, and the
+// caller adapts its share from them (mi_request_split_times).
+int run_split(AsyncJob& j) {
+    const size_t es = dtype_size(j.dt);
+    const void* tail_in[MI_MAX_INPUTS];
+    for (int i = 0; i < j.k; i++) tail_in[i] = static_cast<const char*>(j.inputs[i]) + j.head * es;
+    mi_request_t r = nullptr;
+    const double t0 = mono_s();
+    if (int rc = mi_reduce_start(tail_in, j.k, static_cast<char*>(j.out) + j.head * es, j.count - j.head, j.dt, j.op,
+                                 j.flags, j.device, &r))
+        return rc;
+    size_t chunk = std::max<size_t>(256, ((size_t)8 << 20) / es);
+    chunk -= chunk % 256;
+    int hrc = 0;
+    double t_tail = -1.0;
+    for (size_t b = 0; b < j.head && hrc == 0; b += chunk) {
+        const void* hin[MI_MAX_INPUTS];
+        for (int i = 0; i < j.k; i++) hin[i] = static_cast<const char*>(j.inputs[i]) + b * es;
+        hrc = j.head_fold(hin, j.k, static_cast<char*>(j.out) + b * es, std::min(chunk, j.head - b), j.dt, j.op,
+                          j.flags);
+        int done = 0;
+        if (t_tail < 0 && mi_test(r, &done) == 0 && done) t_tail = mono_s() - t0;
+    }
+    const double t_head = mono_s() - t0;
+    const int wrc = mi_wait(r);
+    if (t_tail < 0) t_tail = mono_s() - t0;
+    (void)mi_request_free(r);
+    if (wrc) return wrc;
+    if (hrc) return fail(hrc, "host fold of the split's head");
+    j.t_head = t_head;  // published to the caller by the job's done flag (under its mutex)
+    j.t_tail = t_tail;
+    return 0;
 }
 
 struct StageWorker {
@@ -1877,7 +1955,7 @@ struct StageWorker {
                     int cur = -1;
                     if (!rc && hipGetDevice(&cur) == hipSuccess) last_device.store(cur, std::memory_order_relaxed);
                     if (!rc)
-                        rc = j->head_fold ? split_job(*j)
+                        rc = j->head_fold ? run_split(*j)
                                           : reduce_sync(j->inputs, j->k, j->out, j->count, j->dt, j->op, j->flags,
                                                         j->device, &j->kinds);
                     j->t_run = mono_s() - t0;  // published by the done flag below
@@ -1913,46 +1991,6 @@ thread_local StageWorker t_stage;
 // This thread has started asynchronous requests that mi_thread_sync has not
 // yet waited for.
 thread_local bool t_async_issued = false;
-
-// A split job, on the staging worker: the GPU part is started from here (a
-// pageable one is staged by this thread's own worker, one level down), the
-// head is folded on this thread meanwhile, then the GPU part is waited for.
-// The head runs in ~8 MiB chunks (multiples of 256 elements, so none holds a
-// keep-precision truncated tail), polling the GPU part between them: both
-// parts' durations are known even when the GPU finishes first, and the
-// caller adapts its share from them (mi_request_split_times).
-
-int run_split(AsyncJob& j) {
-    const size_t es = dtype_size(j.dt);
-    const void* tail_in[MI_MAX_INPUTS];
-    for (int i = 0; i < j.k; i++) tail_in[i] = static_cast<const char*>(j.inputs[i]) + j.head * es;
-    mi_request_t r = nullptr;
-    const double t0 = mono_s();
-    if (int rc = mi_reduce_start(tail_in, j.k, static_cast<char*>(j.out) + j.head * es, j.count - j.head, j.dt, j.op,
-                                 j.flags, j.device, &r))
-        return rc;
-    size_t chunk = std::max<size_t>(256, ((size_t)8 << 20) / es);
-    chunk -= chunk % 256;
-    int hrc = 0;
-    double t_tail = -1.0;
-    for (size_t b = 0; b < j.head && hrc == 0; b += chunk) {
-        const void* hin[MI_MAX_INPUTS];
-        for (int i = 0; i < j.k; i++) hin[i] = static_cast<const char*>(j.inputs[i]) + b * es;
-        hrc = j.head_fold(hin, j.k, static_cast<char*>(j.out) + b * es, std::min(chunk, j.head - b), j.dt, j.op,
-                          j.flags);
-        int done = 0;
-        if (t_tail < 0 && mi_test(r, &done) == 0 && done) t_tail = mono_s() - t0;
-    }
-    const double t_head = mono_s() - t0;
-    const int wrc = mi_wait(r);
-    if (t_tail < 0) t_tail = mono_s() - t0;
-    (void)mi_request_free(r);
-    if (wrc) return wrc;
-    if (hrc) return fail(hrc, "host fold of the split's head");
-    j.t_head = t_head;  // published to the caller by the job's done flag (under its mutex)
-    j.t_tail = t_tail;
-    return 0;
-}
 
 // Events behind the work the calling thread has queued on its own streams
 // (every device it used); streams that are already idle need none.
@@ -2250,54 +2288,19 @@ int mi_convert_sync(const void* src, int src_dtype, void* dst, int dst_dtype, si
             MI_HIP(wait_stream(d->stream[0]));
             return 0;
         }
-        const size_t ss = dtype_size(src_dtype), ds = dtype_size(dst_dtype);
-        size_t chunk = kChunkBytes / std::max(ss, ds);
-        chunk -= chunk % 16;
-        rc = ensure_scratch(d, 2, chunk * std::max(ss, ds) + kStageSlack);
+        const StagedOp ops[2] = {{src, ks, dtype_size(src_dtype)}, {dst, kd, dtype_size(dst_dtype)}};
+        int used = 0;
+        rc = staged_pipeline(
+            d, ops, 1, count, " (conversion)",
+            [&](size_t off, size_t n, const void* const* dsrc, void* ddst, hipStream_t st) {
+                // the chunk's window of the whole array's tail split (stage_chunk_elems)
+                return launch_convert(dsrc[0], src_dtype, ddst, dst_dtype, n, flags, st,
+                                      trunc_from > off ? std::min<uint64_t>(trunc_from - off, n) : 0);
+            },
+            &used, nullptr, nullptr);
         if (rc) return rc;
-        Edges edges;  // unaligned ends of D2H copies into pageable memory (d2h_pageable)
-        if (kd == PK_PAGEABLE) {
-            rc = ensure_edges(d);
-            if (rc) return rc;
-            edges.pin = d->edge;
-            edges.slots = kDrainEdge / kEdgeSlot;
-        }
-        for (size_t off = 0, c = 0; off < count; off += chunk, c++) {
-            const int sl = (int)(c & 1);
-            hipStream_t st = d->stream[sl];
-            const size_t n = std::min(chunk, count - off);
-            const void* sp = static_cast<const char*>(src) + off * ss;
-            void* dp = static_cast<char*>(dst) + off * ds;
-            const void* dsrc = sp;
-            void* ddst = dp;
-            if (ks != PK_DEVICE) {
-                size_t sh = 0;
-                if (hipError_t he = h2d_stage(d->dbuf[sl][0], sp, n * ss, st, &sh))
-                    return copy_fail(he, "H2D staging copy (conversion)", sp, n * ss, c, ks, true);
-                dsrc = static_cast<const char*>(d->dbuf[sl][0]) + sh;
-            }
-            if (kd != PK_DEVICE)
-                ddst = static_cast<char*>(d->dbuf[sl][1]) + (reinterpret_cast<uintptr_t>(dp) & (kHostAlign - 1));
-            // chunk starts are multiples of 16: the tail split is the global one
-            rc = launch_convert(dsrc, src_dtype, ddst, dst_dtype, n, flags, st,
-                                trunc_from > off ? std::min<uint64_t>(trunc_from - off, n) : 0);
-            if (rc) return rc;
-            if (kd == PK_PAGEABLE) {
-                if (edges.full()) {
-                    MI_HIP(wait_stream(d->stream[0]));
-                    MI_HIP(wait_stream(d->stream[1]));
-                    edges.flush();
-                }
-                if (hipError_t he = d2h_pageable(dp, ddst, n * ds, st, edges))
-                    return copy_fail(he, "D2H result copy (conversion)", dp, n * ds, c, kd, false);
-            } else if (kd != PK_DEVICE) {
-                if (hipError_t he = hipMemcpyAsync(dp, ddst, n * ds, hipMemcpyDeviceToHost, st))
-                    return copy_fail(he, "D2H result copy (conversion)", dp, n * ds, c, kd, true);
-            }
-        }
         MI_HIP(wait_stream(d->stream[0]));
         MI_HIP(wait_stream(d->stream[1]));
-        edges.flush();
         return 0;
     });
 }
@@ -2647,8 +2650,7 @@ int mi_copy_sync(const void* src, void* dst, size_t bytes, int nontemporal, int 
             rc = ensure_edges(d);
             if (rc) return rc;
             Edges edges;
-            edges.pin = d->edge;
-            edges.slots = 1;
+            edges.open(d->edge, 1);
             if (kd == PK_PAGEABLE) {
                 if (hipError_t he = d2h_pageable(dst, src, bytes, st, edges))
                     return copy_fail(he, "D2H copy (mi_copy_sync)", dst, bytes, 0, kd, false);
@@ -2656,24 +2658,7 @@ int mi_copy_sync(const void* src, void* dst, size_t bytes, int nontemporal, int 
                 edges.flush();
                 return 0;
             }
-            // pageable -> device: the ends through pinned scratch, the aligned interior direct
-            const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-            const size_t head = std::min(bytes, (size_t)(host_align_up(a) - a));
-            const size_t interior = (bytes - head) & ~(size_t)(kHostAlign - 1);
-            const size_t tail = bytes - head - interior;
-            const char* s8 = static_cast<const char*>(src);
-            char* d8 = static_cast<char*>(dst);
-            if (head) {
-                memcpy(edges.pin, s8, head);
-                MI_HIP(hipMemcpyAsync(d8, edges.pin, head, hipMemcpyHostToDevice, st));
-            }
-            if (interior)
-                if (hipError_t he = hipMemcpyAsync(d8 + head, s8 + head, interior, hipMemcpyHostToDevice, st))
-                    return copy_fail(he, "H2D copy (mi_copy_sync)", src, bytes, 0, ks, false);
-            if (tail) {
-                memcpy(edges.pin + kHostAlign, s8 + head + interior, tail);
-                MI_HIP(hipMemcpyAsync(d8 + head + interior, edges.pin + kHostAlign, tail, hipMemcpyHostToDevice, st));
-            }
+            if ((rc = h2d_pageable(dst, src, bytes, st, edges))) return rc;
             MI_HIP(wait_stream(st));
             return 0;
         }

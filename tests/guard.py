@@ -47,7 +47,8 @@ mi_reduce.hip and host_reduce*.cpp; knob = how the test routes to it):
   zero-copy (pinned)       test_gpu_host_bounds::test_zero_copy_pinned (mi_reduce_sync, mi_reduce_multi_sync)
   bounce buffers           test_gpu_host_bounds::test_bounce_buffers (pageable, at most 1 MiB)
   staged pipeline, Edges   test_gpu_host_bounds::test_staged_pipeline_one_chunk, _two_chunks (pageable, above 1 MiB)
-  mi_copy_sync / convert   test_gpu_host_bounds::test_copy_sync_into_host, test_convert_sync_into_host
+  mi_copy_sync / convert   test_gpu_host_bounds::test_copy_sync_into_host, test_convert_sync_into_host,
+                           test_convert_sync_two_chunks (d2h_pageable; staged_pipeline's second chunk)
   mi_reduce_start, split   test_gpu_host_bounds::test_start_wait, test_split_start
   drop-in on host buffers  test_gpu_host_bounds::test_dropin_*_on_host_buffers (CCL_COMP_HOST_MAX_BYTES=0, default)
   CPU host path            test_host_bounds (mi_host_reduce, mi_host_convert, mi_host_copy, the drop-in's

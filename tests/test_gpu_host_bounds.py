@@ -173,6 +173,29 @@ def test_convert_sync_into_host(kind, sdt, ddt, flags):
         assert np.array_equal(ar.read(pd).view(np.uint8), exp.view(np.uint8)), case
 
 
+@pytest.mark.parametrize("sdt,ddt,flags,smis,dmis", [(FP32, BF16, F_BF16_RNE | F_BF16_TAIL_TRUNC16, 4, 2),
+                                                     (BF16, FP32, 0, 2, 4)], ids=["f32-bf16rne-tail", "bf16-f32"])
+def test_convert_sync_two_chunks(sdt, ddt, flags, smis, dmis):
+    """A staged conversion across a chunk boundary.  The chunk is 32 MiB of
+    the larger element, 8388608 elements; 23 more make a second chunk whose
+    first 16 elements are rounded and whose last 7 are truncated under
+    F_BF16_TAIL_TRUNC16 (count // 16 * 16 lies inside it): the smallest count
+    that crosses the boundary and puts the split into the second chunk's
+    window.  Source and destination sit off 16-byte alignment by different
+    amounts, so both chunks' staged copies have unaligned ends."""
+    n = 8388608 + 23
+    ss, ds = _es(sdt), _es(ddt)
+    ar = Arena(arena_bytes(n * (ss + ds), 2), "pageable", seed=4)
+    src = rand_array(sdt, n, seed=400)
+    ps = ar.place(src, smis, "in", "src")
+    pd = ar.place(np.full(n * ds, 0x5A, np.uint8).view(np.uint32 if ds == 4 else np.uint16), dmis, "out", "dst")
+    exp = convert_expected(src, sdt, ddt, flags)
+    ar.snapshot()
+    _lib.check(_lib.mi().mi_convert_sync(ps.ptr, sdt, pd.ptr, ddt, n, flags, -1), "mi_convert_sync")
+    ar.check(what="mi_convert_sync over two chunks")
+    assert np.array_equal(ar.read(pd).view(np.uint8), exp.view(np.uint8))
+
+
 # ---- requests -----------------------------------------------------------------
 
 def _host_fold_ptr():

@@ -1,7 +1,7 @@
 """Pageable operands at every 16-byte misalignment through the paths that
 hand host memory to the runtime's copies (mi_reduce.hip, h2d_stage /
-d2h_pageable): the staged reduce (in place and out of place, 2 and 3
-inputs, one chunk and several), the staged conversions and mi_copy_sync in
+d2h_pageable / h2d_pageable over host_span.hpp): the staged reduce (in
+place and out of place, 2 and 3 inputs, one chunk and several), the staged conversions and mi_copy_sync in
 both directions.  Each operand ends at (or starts at) a PROT_NONE guard
 page, so a copy that read or wrote past the operand's pages would fault on
 the host; the runtime is given 16-byte-aligned host spans only, which never
