@@ -217,6 +217,62 @@ int mi_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, 
                            size_t count, int dtype, int op, unsigned flags,
                            double scale, void* stream);
 
+/* Fold k inputs of one precision in fp32 and write the sum in another to m
+ * outputs, in one pass.  The supported (in_dtype, out_dtype) pairs are
+ * exactly bf16 -> fp32 and fp16 -> fp32 (widening) and fp32 -> bf16 and
+ * fp32 -> fp16 (narrowing); op == MI_OP_SUM only.  Every output holds exactly
+ * the bytes this composition of existing calls writes, NaN payloads included:
+ *   Widening.  Let c_j be what mi_convert(inputs[j], in_dtype -> fp32) writes
+ * (bf16: a shift; fp16: VCVTPH2PS, which quiets a signalling NaN).  With
+ * acc == NULL, outs[i] = mi_reduce_multi({c_0 .. c_{k-1}}, fp32, sum) for
+ * 1 <= k <= 16 (k = 1 is the conversion).  With acc != NULL (fp32, count
+ * elements) acc is the accumulator's start: outs[i] = mi_reduce_multi({acc,
+ * c_0 .. c_{k-1}}, fp32, sum), for 1 <= k and k + 1 <= MI_MAX_INPUTS.  No
+ * flag changes a bit here (no final rounding, and a sum has no operand-order
+ * variant); flags are canonicalised as everywhere and otherwise ignored.
+ * This is the fp32 accumulator of the MI_F_ACC_FP32 fold before its one
+ * rounding: narrowing the acc == NULL result with mi_convert under the flags'
+ * rounding bits gives mi_reduce_multi(inputs, in_dtype, sum, MI_F_ACC_FP32 |
+ * those bits) bit for bit (tests/test_mixed_expected.py: bf16 under 0x4-0x7,
+ * fp16 under 0x4 / 0x5, k = 1, 2, 3, 8, 16).  It is what the reference's
+ * keep-precision batch reduce holds in its fp32 scratch array before it
+ * rounds and discards it (src/comp/comp.cpp:214-234).
+ *   Narrowing.  F = mi_reduce_multi(inputs, fp32, sum), 1 <= k <= 16; then
+ * outs[i] = mi_convert(F, fp32 -> out_dtype, flags): bf16 truncation, or
+ * MI_F_BF16_RNE (VCVTNEPS2BF16), or MI_F_BF16_RNE | MI_F_BF16_TAIL_TRUNC16
+ * (the last count % 16 elements truncate); fp16 round to nearest even.
+ * k = 1 is the conversion.  acc must be NULL.
+ *   Against the sequences it replaces (k mi_convert calls into k scratch
+ * buffers and an fp32 mi_reduce_bcast: 10k + 4m bytes per element, k + 1
+ * dispatches; mi_reduce_multi into an fp32 scratch buffer and m mi_convert
+ * calls: 4k + 4 + 6m bytes, 1 + m dispatches) it moves 2k + 4m and 4k + 2m
+ * bytes per element in one dispatch and needs no scratch buffer.
+ *   Asynchronous on `stream`; device pointers or device-visible pinned host
+ * pointers (a pageable operand is refused as by mi_reduce_bcast); one kernel
+ * node in a HIP graph.  Refused before any HIP call, with a message naming
+ * the operand or argument.  MI_E_UNSUPPORTED: a dtype pair outside the four
+ * above, equal dtypes included (that is mi_reduce_bcast); an op other than
+ * sum; acc != NULL when narrowing.  MI_E_INVALID: a NULL list or entry; k or
+ * m out of range (acc counts against MI_MAX_INPUTS); an address that
+ * overflows; two outputs whose byte ranges overlap; an output that overlaps
+ * any input at all (the element sizes differ, so there is no in-place form
+ * with them; ranges are computed with each side's own element size); an
+ * output that overlaps acc without being equal to it.  acc may be exactly one
+ * output: the in-place main_grad += sum of the wire gradients (each lane has
+ * acc's and all k loads back before its first store, and loads exactly the
+ * bytes it stores).  count == 0 returns 0 after the checks.  Outputs at
+ * differing misalignments mod 16, operands not aligned to their element
+ * size, and, under mi_set_unaligned_vectors(0), inputs off the outputs' grid
+ * take the element loop (same bits).
+ *   Not provided: a _sync, staged or pageable form, a request form, a host-CPU
+ * path, a drop-in C++ symbol or a patch under integration/, a scale, ops
+ * other than sum, fp64 and integer types, peer-GPU destinations (untested, as
+ * for mi_reduce_bcast).  mi_version() is unchanged: the symbol's presence is
+ * how a caller detects the entry point.                                     */
+int mi_reduce_bcast_mixed(const void* const* inputs, int k, int in_dtype,
+                          const void* acc, void* const* outs, int m, int out_dtype,
+                          size_t count, int op, unsigned flags, void* stream);
+
 /* n independent mi_reduce calls in one dispatch: descs[i].inout =
  * op(descs[i].in, descs[i].inout) over descs[i].count elements, all with one
  * dtype / op / flags.  Results are those of the n mi_reduce calls in any
@@ -470,7 +526,10 @@ int mi_get_residency(int device, int k, int* waves_per_cu, unsigned* lds_bytes);
  * streams in flight per wave, s = min(k + m - 1, 16): the fan-in's plan for
  * s inputs up to 12, 6 waves above; mi_set_residency(s, ...) overrides it.
  * mi_reduce_bcast_scaled plans every (k, m) that way, m = 1 included, but
- * (2, 1), which takes the 2-input kernel's plan (k = 2 above).              */
+ * (2, 1), which takes the 2-input kernel's plan (k = 2 above).
+ * mi_reduce_bcast_mixed plans likewise, by s = min(k + acc + m - 1, 16) with
+ * acc = 1 when an accumulator is given, and by the 2-input kernel's plan for
+ * two loads and one store per lane (k + acc = 2, m = 1).                     */
 int mi_set_residency(int k, int waves_per_cu);
 /* Store policy of mi_reduce_bcast's vector stores (tuning knob): 1 (default)
  * = sc1 + nt, as the 2-input kernel stores (the line leaves L2 as it is

@@ -22,6 +22,7 @@ from .comp import (  # noqa: F401
     impl_types,
     reduce,
     reduce_bcast,
+    reduce_bcast_mixed,
     reduce_bcast_scaled,
     reduce_multi,
     reduce_out,

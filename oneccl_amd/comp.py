@@ -204,6 +204,49 @@ def reduce_bcast_scaled(inputs: Sequence, outs: Sequence, scale: float, flags: O
           "mi_reduce_bcast_scaled")
 
 
+def reduce_bcast_mixed(inputs: Sequence, outs: Sequence, acc=None, flags: Optional[int] = None,
+                       stream=None) -> None:
+    """Every tensor of `outs` = the fp32 sum over `inputs` (on top of the fp32
+    tensor `acc`, if given), stored in the outputs' precision, in one pass
+    (mi_reduce_bcast_mixed).  bf16 or fp16 inputs with fp32 outputs, or fp32
+    inputs with bf16 or fp16 outputs (no `acc` then); the dtypes are the
+    tensors'.  `acc` may be one of the outputs; no output may overlap an input.
+    flags=None: reference_flags of the 16-bit dtype."""
+    inputs, outs = list(inputs), list(outs)
+    if not inputs or not outs:
+        raise ValueError("reduce_bcast_mixed needs at least one input and one output")
+    t0, o0 = inputs[0], outs[0]
+    for group, first, what in ((inputs, t0, "inputs"), (outs, o0, "outputs")):
+        for t in group:
+            if t.dtype != first.dtype:
+                raise TypeError(f"all {what} must have one dtype ({t.dtype} against {first.dtype})")
+    idt, odt = _torch_ccl_dtype(t0), _torch_ccl_dtype(o0)
+    lp = (datatype.bfloat16, datatype.float16)
+    if not ((idt in lp and odt == datatype.float32) or (idt == datatype.float32 and odt in lp)):
+        raise TypeError(f"unsupported dtype pair {t0.dtype} -> {o0.dtype}: bf16 / fp16 inputs with fp32 outputs, or "
+                        "fp32 inputs with bf16 / fp16 outputs (equal dtypes: reduce_bcast)")
+    if acc is not None:
+        if odt != datatype.float32:
+            raise TypeError("acc goes with fp32 outputs only")
+        if _torch_ccl_dtype(acc) != datatype.float32:
+            raise TypeError(f"acc must be float32 ({acc.dtype})")
+    every = inputs + outs + ([acc] if acc is not None else [])
+    for t in every:
+        if t.numel() != t0.numel():
+            raise ValueError(f"all tensors must have the same numel ({t.numel()} against {t0.numel()})")
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+        if t.device != t0.device:
+            raise ValueError(f"all tensors must be on one device ({t.device} against {t0.device})")
+    if not t0.is_cuda:
+        raise ValueError("device entry points take device tensors")
+    f = reference_flags(idt if idt in lp else odt) if flags is None else flags
+    check(mi().mi_reduce_bcast_mixed(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), int(idt),
+                                     acc.data_ptr() if acc is not None else None,
+                                     void_ptr_array([t.data_ptr() for t in outs]), len(outs), int(odt), t0.numel(),
+                                     int(reduction.sum), f, _stream_handle(stream)), "mi_reduce_bcast_mixed")
+
+
 # ---- the drop-in shim (synchronous, host or device pointers) ------------
 
 def comp_reduce(in_ptr: int, count: int, inout_ptr: int, dtype: datatype, op: reduction) -> Optional[int]:

@@ -899,6 +899,170 @@ int launch_reduce_bcast_scaled(const void* const* inputs, int k, void* const* ou
 }
 
 // ---------------------------------------------------------------------------
+// fold in fp32 across precisions, write to m outputs (mi_reduce_bcast_mixed)
+// ---------------------------------------------------------------------------
+// Lane layout of the mixed kernels' tiles: a wave's 512 elements as two runs
+// of 4 per lane (convert_kernel's wave chunks).  The alternative, one run of 4
+// per lane, is the same kernel text with RUNS = 1; as compiled it took 238 VGPRs
+// (fp32 in, 8 slots) and 492 with scratch (16-bit in, 16 slots), so it is not
+// built and was not measured.
+constexpr int kMixedRuns = 2;
+
+typedef hipError_t (*LaunchMxFn)(unsigned stride_blocks, unsigned tiles, hipStream_t, const MXArgs&, unsigned lds);
+
+// stride_blocks = 0: one tile per one-wave block (8 input slots for k <= 8,
+// else 16), capped by `lds` like the fan-out.  Otherwise the grid-stride form
+// with that many blocks (a grid cap, or the element loop).
+template <typename ST, typename DT, unsigned V, int RUNS>
+hipError_t launch_mixed(unsigned stride_blocks, unsigned tiles, hipStream_t s, const MXArgs& a, unsigned lds) {
+    if (stride_blocks)
+        hipLaunchKernelGGL((mixed_stride_kernel<ST, DT, V, RUNS>), dim3(stride_blocks), dim3(kMixedBlock), 0, s, a);
+    else if (a.k <= 8)
+        hipLaunchKernelGGL((mixed_kernel<ST, DT, V, RUNS, 8>), dim3(tiles), dim3(kMixedBlock), lds, s, a);
+    else
+        hipLaunchKernelGGL((mixed_kernel<ST, DT, V, RUNS, kMaxInputs>), dim3(tiles), dim3(kMixedBlock), lds, s, a);
+    return hipGetLastError();
+}
+
+LaunchMxFn pick_mixed(int idt, int odt, unsigned v) {
+    constexpr int RUNS = kMixedRuns;
+    if (idt == MI_BFLOAT16) return &launch_mixed<bf16_tag, float, 0u, RUNS>;
+    if (idt == MI_FLOAT16) return &launch_mixed<fp16_tag, float, 0u, RUNS>;
+    if (odt == MI_FLOAT16) return &launch_mixed<float, fp16_tag, 0u, RUNS>;
+    if (!(v & V_BF16_RNE)) return &launch_mixed<float, bf16_tag, 0u, RUNS>;
+    return (v & V_TAIL_TRUNC) ? &launch_mixed<float, bf16_tag, V_BF16_RNE | V_TAIL_TRUNC, RUNS>
+                              : &launch_mixed<float, bf16_tag, V_BF16_RNE, RUNS>;
+}
+
+// Every refusal, before any HIP call.  Ranges are computed with each side's
+// own element size; an output may overlap no input at all (the element sizes
+// differ, so no lane would load exactly the bytes it stores), and `acc` only
+// by being it.
+int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void* acc, void* const* outs, int m,
+                     size_t es_out, size_t count) {
+    char msg[160];
+    for (int i = 0; i < k; i++)
+        if (!inputs[i]) {
+            snprintf(msg, sizeof(msg), "inputs[%d] is NULL", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    for (int i = 0; i < m; i++)
+        if (!outs[i]) {
+            snprintf(msg, sizeof(msg), "outs[%d] is NULL", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    if (count == 0) return 0;
+    if (count > UINTPTR_MAX / 4) return fail(MI_E_INVALID, "count overflows the address space");
+    const uintptr_t nbi = count * es_in, nbo = count * es_out, nba = count * 4;
+    for (int i = 0; i < k; i++)
+        if (nbi > UINTPTR_MAX - reinterpret_cast<uintptr_t>(inputs[i])) {
+            snprintf(msg, sizeof(msg), "inputs[%d] + count overflows the address space", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    const uintptr_t al = reinterpret_cast<uintptr_t>(acc);
+    if (acc && nba > UINTPTR_MAX - al) return fail(MI_E_INVALID, "acc + count overflows the address space");
+    for (int i = 0; i < m; i++)
+        if (nbo > UINTPTR_MAX - reinterpret_cast<uintptr_t>(outs[i])) {
+            snprintf(msg, sizeof(msg), "outs[%d] + count overflows the address space", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    for (int i = 0; i < m; i++) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(outs[i]), hi = lo + nbo;
+        for (int j = 0; j < i; j++) {
+            const uintptr_t l2 = reinterpret_cast<uintptr_t>(outs[j]);
+            if (lo < l2 + nbo && l2 < hi) {
+                snprintf(msg, sizeof(msg), "outs[%d] and outs[%d] overlap", j, i);
+                return fail(MI_E_INVALID, msg);
+            }
+        }
+        for (int j = 0; j < k; j++) {
+            const uintptr_t l2 = reinterpret_cast<uintptr_t>(inputs[j]);
+            if (lo < l2 + nbi && l2 < hi) {
+                snprintf(msg, sizeof(msg), "outs[%d] overlaps inputs[%d] (no in-place form across element sizes)", i, j);
+                return fail(MI_E_INVALID, msg);
+            }
+        }
+        if (acc && al != lo && lo < al + nba && al < hi) {
+            snprintf(msg, sizeof(msg), "outs[%d] overlaps acc without being equal to it", i);
+            return fail(MI_E_INVALID, msg);
+        }
+    }
+    return 0;
+}
+
+int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m,
+                              int odt, size_t count, int op, unsigned flags, hipStream_t stream) {
+    const bool widening = (idt == MI_BFLOAT16 || idt == MI_FLOAT16) && odt == MI_FLOAT32;
+    const bool narrowing = idt == MI_FLOAT32 && (odt == MI_BFLOAT16 || odt == MI_FLOAT16);
+    if (!widening && !narrowing)
+        return fail(MI_E_UNSUPPORTED,
+                    "in_dtype/out_dtype: the pairs are bf16->fp32, fp16->fp32, fp32->bf16, fp32->fp16 "
+                    "(equal dtypes: mi_reduce_bcast)");
+    if (op != MI_OP_SUM) return fail(MI_E_UNSUPPORTED, "op: a mixed-precision reduction is a sum (MI_OP_SUM)");
+    if (acc && narrowing) return fail(MI_E_UNSUPPORTED, "acc: an accumulator is fp32, so only a widening call takes one");
+    const int kmax = MI_MAX_INPUTS - (acc ? 1 : 0);
+    if (k < 1 || k > kmax)
+        return fail(MI_E_INVALID, acc ? "input count k out of range [1,15] (acc counts against MI_MAX_INPUTS)"
+                                      : "input count k out of range [1,16]");
+    if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
+    if (!inputs) return fail(MI_E_INVALID, "null input list");
+    if (!outs) return fail(MI_E_INVALID, "null output list");
+    const size_t es_in = dtype_size(idt), es_out = dtype_size(odt);
+    if (int rc = check_mixed_args(inputs, k, es_in, acc, outs, m, es_out, count)) return rc;
+    if (count == 0) return 0;
+
+    for (int i = 0; i < k; i++)
+        if (int rc = require_gpu_visible(inputs[i], count * es_in)) return rc;
+    if (acc)
+        if (int rc = require_gpu_visible(acc, count * 4)) return rc;
+    for (int i = 0; i < m; i++)
+        if (int rc = require_gpu_visible(outs[i], count * es_out)) return rc;
+
+    // the variant bits that change a bit: the narrowing conversion's (canon_flags)
+    const unsigned v = narrowing ? (canon_flags(odt, op, flags | V_ACC_FP32, k) & (V_BF16_RNE | V_TAIL_TRUNC)) : 0u;
+    const LaunchMxFn fn = pick_mixed(idt, odt, v);
+
+    const MixedGrid g = plan_mixed_grid(es_in, es_out, count, outs, m, inputs, k, acc, unaligned_vectors() != 0);
+    MXArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < k; i++) a.in[i] = inputs[i];
+    for (int i = 0; i < m; i++) a.out[i] = outs[i];
+    a.acc = acc;
+    a.k = k;
+    a.m = m;
+    a.count = count;
+    a.trunc_from = (count / 16) * 16;
+    a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
+    a.head = g.head;
+    a.ngroups = g.ngroups;
+    a.tail = g.tail;
+    a.scalar_only = !g.vec;
+    const uint64_t te = mixed_tile_elems<kMixedRuns>();
+    const uint64_t tiles = std::max<uint64_t>((g.ngroups * 8 + te - 1) / te, 1);
+    const int cap = max_blocks();
+    hipError_t e;
+    if (g.vec && cap == 0 && tiles <= 0x7FFFFFFFull) {
+        // The fan-out's residency plan by streams, acc one of them, but for two
+        // loads and one store per lane, which is the 2-input reduce's stream and
+        // wants that kernel's plan (21 waves per CU, as mi_reduce_bcast_scaled's
+        // (2, 1)): 1 GiB of fp32 from two bf16 inputs ran at 0.335 ms at the
+        // fan-out's 16 waves and at 0.314 at 21; fp32 to bf16 the same within 1 %
+        // at 12, 16 and 21.  At the other shapes measured ((8, 1), (8, 1) with
+        // acc, (2, 2), (8, 8)) the plan was the fastest or within 2 % of it
+        // (tools/mixed_sweep.py --residency, profiles/reduce_mixed/).
+        const int ks = k + (acc ? 1 : 0);
+        const int waves = (ks == 2 && m == 1) ? planned_waves(2) : bcast_planned_waves(ks, m);
+        e = fn(0u, (unsigned)tiles, stream, a, wave_cap_lds(stream, waves));
+    } else {
+        uint64_t blocks = g.vec ? tiles : std::min<uint64_t>((count + kMixedBlock - 1) / kMixedBlock, 8192);
+        if (g.vec && cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
+        e = fn((unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull), 0u, stream, a, 0u);
+    }
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // descriptor batch: independent 2-input reduces in one launch
 // ---------------------------------------------------------------------------
 // Outputs must be pairwise disjoint and disjoint from other descriptors'
@@ -2177,6 +2341,12 @@ int mi_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, 
 int mi_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dtype,
                            int op, unsigned flags, double scale, void* stream) {
     return launch_reduce_bcast_scaled(inputs, k, outs, m, count, dtype, op, flags, scale, (hipStream_t)stream);
+}
+
+int mi_reduce_bcast_mixed(const void* const* inputs, int k, int in_dtype, const void* acc, void* const* outs, int m,
+                          int out_dtype, size_t count, int op, unsigned flags, void* stream) {
+    return launch_reduce_bcast_mixed(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags,
+                                     (hipStream_t)stream);
 }
 
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op, unsigned flags,

@@ -1373,6 +1373,333 @@ __global__ __launch_bounds__(B) void convert_kernel(CArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// mi_reduce_bcast_mixed: fold K inputs of one precision in fp32 and write the
+// result in the other, to M outputs, in one pass.  Widening (bf16 / fp16 in,
+// fp32 out, optionally on top of an fp32 accumulator `acc`) is the fp32
+// scratch fold of the reference's keep-precision batch reduce
+// (src/comp/comp.cpp:214-234) without the rounding that ends it; narrowing
+// (fp32 in, bf16 / fp16 out) is the fp32 fan-in followed by the array
+// conversion.  The pieces are the ones above: convert_elem (the fp16
+// signalling-NaN quieting included), step<float, OP_SUM> with the accumulator
+// as first source, finish<DT, V> with the element-indexed trunc_from, per-tile
+// buffer descriptors, the wave-uniform store loop.
+//   Geometry: launch_convert's plan (plan_mixed_grid, vec_grid.hpp).  The body
+// is groups of 8 elements from the outputs' first 16-byte boundary on.  A
+// one-wave block owns a tile of 64 * RUNS runs of 4 elements; lane L takes
+// run r * 64 + L for r < RUNS, so every load and store instruction covers one
+// contiguous span across the wave (8 bytes per lane on the 16-bit side, 16 on
+// the fp32 side), as convert_kernel's wave chunks do.  RUNS = 2 is that
+// kernel's layout (512 elements per wave, 8 per lane) and the one built;
+// RUNS = 1 would be 4 elements per lane (256 per wave).  A tile's valid elements
+// are a multiple of 8, so a run is wholly inside its descriptors or wholly
+// outside (loads zeros, stores dropped).
+//   Every lane has all k loads (and acc's) issued before its first combine and
+// back before its first store; `acc` may be exactly one output (both fp32, so
+// it sits on the outputs' grid and a lane loads exactly the bytes it later
+// stores): mi_reduce_bcast's in-place argument.
+// ---------------------------------------------------------------------------
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+struct MXArgs {
+    const void* in[kMaxInputs];
+    void* out[kMaxInputs];  // m destinations, all at one misalignment on the vector path
+    const void* acc;        // widening: the fp32 accumulator's start, or null
+    uint64_t ngroups;       // groups of 8 elements in the body
+    uint64_t head;          // leading scalar elements (the outputs' misalignment)
+    uint64_t tail;          // trailing scalar elements (< 8)
+    uint64_t count;         // total elements
+    uint64_t trunc_from;    // V_TAIL_TRUNC threshold (element index)
+    int k;                  // inputs (acc not counted)
+    int m;                  // outputs
+    int scalar_only;        // element loop only
+    int store_sc1;          // stores sc1 + nt instead of nt (mi_set_bcast_store)
+};
+
+constexpr int kMixedBlock = 64;  // one wave
+template <int RUNS>
+constexpr uint32_t mixed_tile_elems() {
+    return 4u * kMixedBlock * RUNS;
+}
+
+// One run of 4 elements as loaded: 8 bytes of a 16-bit type, 16 of fp32.
+template <typename T>
+struct MxRun {
+    using type = typename std::conditional<sizeof(typename Tr<T>::S) == 2, u32x2, u32x4>::type;
+};
+
+template <typename T>
+__device__ __forceinline__ typename MxRun<T>::type mx_load(__amdgpu_buffer_rsrc_t rs, uint32_t off) {
+    if constexpr (sizeof(typename Tr<T>::S) == 2)
+        return __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, kAuxNT);
+    else
+        return __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, kAuxNT);
+}
+
+// The run's 4 values in fp32: what mi_convert(T -> fp32) writes (X: with the
+// fp16 signalling-NaN quieting), or the words themselves.
+template <typename T, bool X>
+__device__ __forceinline__ void mx_widen(const typename MxRun<T>::type& x, float (&f)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+        if constexpr (sizeof(typename Tr<T>::S) == 2)
+            f[e] = convert_elem<T, float, 0u, X>((uint16_t)(x[e >> 1] >> (16 * (e & 1))), 0, 0);
+        else
+            f[e] = __uint_as_float(x[e]);
+    }
+}
+
+// inf_nan_bits of one run (all-ones exponent: Inf or NaN)
+template <typename T>
+__device__ __forceinline__ bool mx_inf_nan(const typename MxRun<T>::type& x) {
+    if constexpr (sizeof(typename Tr<T>::S) == 2)
+        return inf_nan_hit<T>(inf_nan_word<T>(x.x) | inf_nan_word<T>(x.y));
+    else
+        return inf_nan_hit<float>(inf_nan_word<float>(x.x) | inf_nan_word<float>(x.y) | inf_nan_word<float>(x.z) |
+                                  inf_nan_word<float>(x.w));
+}
+
+// The fold of one run of 4 elements across the loaded inputs (and acc), and
+// its final conversion.  e0: the run's first element index.
+template <typename ST, typename DT, unsigned V, bool X, int KMAX>
+__device__ __forceinline__ typename MxRun<DT>::type mx_fold(const typename MxRun<ST>::type (&x)[KMAX], int k,
+                                                            bool has_acc, u32x4 xa, uint64_t e0,
+                                                            uint64_t trunc_from) {
+    float s[4], c[4];
+    if (has_acc) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) s[e] = __uint_as_float(xa[e]);
+    }
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+        if (i < k) {
+            mx_widen<ST, X>(x[i], c);
+            if (i == 0 && !has_acc) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) s[e] = c[e];
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; e++) s[e] = step<float, OP_SUM, 0u, X>(c[e], s[e]);
+            }
+        }
+    }
+    typename MxRun<DT>::type r;
+    if constexpr (std::is_same<DT, float>::value) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) r[e] = __float_as_uint(s[e]);
+    } else {
+        uint32_t h[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) h[e] = finish<DT, V, X>(s[e], e0 + e, trunc_from);
+        r.x = h[0] | (h[1] << 16);
+        r.y = h[2] | (h[3] << 16);
+    }
+    return r;
+}
+
+// Element `idx` on the scalar path (head, tail, element loop), stored to every
+// output.
+template <typename ST, typename DT, unsigned V>
+__device__ __forceinline__ void mixed_elem(const MXArgs& a, uint64_t idx) {
+    using SS = typename Tr<ST>::S;
+    using DS = typename Tr<DT>::S;
+    const auto c = [&](int j) -> float {
+        if constexpr (sizeof(SS) == 2)
+            return convert_elem<ST, float, 0u, true>(static_cast<const SS*>(a.in[j])[idx], 0, 0);
+        else
+            return static_cast<const float*>(a.in[j])[idx];
+    };
+    float s;
+    int j = 0;
+    if (a.acc) s = static_cast<const float*>(a.acc)[idx];
+    else s = c(j++);
+    for (; j < a.k; j++) s = step<float, OP_SUM, 0u, true>(c(j), s);
+    DS r;
+    if constexpr (std::is_same<DT, float>::value) r = s;
+    else r = finish<DT, V, true>(s, idx, a.trunc_from);
+    for (int o = 0; o < a.m; o++) static_cast<DS*>(a.out[o])[idx] = r;
+}
+
+// A tile's geometry: its first element and its valid elements (a multiple of
+// 8; 0 for a tile past the end).
+template <int RUNS>
+__device__ __forceinline__ void mx_tile_of(const MXArgs& a, uint64_t tile, uint64_t& first, uint32_t& ne) {
+    constexpr uint32_t TE = mixed_tile_elems<RUNS>();
+    const uint64_t t0 = tile * TE, nbody = a.ngroups * 8;
+    const uint64_t left = nbody > t0 ? nbody - t0 : 0;
+    ne = (uint32_t)(left < (uint64_t)TE ? left : (uint64_t)TE);
+    first = a.head + t0;
+}
+
+// This lane's byte offset of run r in a tile of elements of `es` bytes.
+__device__ __forceinline__ uint32_t mx_off(int r, uint32_t es) {
+    return (uint32_t)(r * kMixedBlock + threadIdx.x) * 4u * es;
+}
+
+// The m stores of a lane's results: bcast_store's wave-uniform loop over the
+// output pointers, one descriptor per output.
+template <typename DT, int RUNS>
+__device__ __forceinline__ void mx_store(const MXArgs& a, int m, const typename MxRun<DT>::type (&res)[RUNS],
+                                         uint64_t first, uint32_t ne) {
+    using DS = typename Tr<DT>::S;
+    const auto store = [&](auto aux) {
+#pragma nounroll
+        for (int o = 0; o < m; o++) {
+            const __amdgpu_buffer_rsrc_t rs = tile_rsrc(a.out[o], first * sizeof(DS), ne * (uint32_t)sizeof(DS));
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) {
+                if constexpr (sizeof(DS) == 2)
+                    __builtin_amdgcn_raw_buffer_store_b64(res[r], rs, mx_off(r, 2), 0, decltype(aux)::value);
+                else
+                    __builtin_amdgcn_raw_buffer_store_b128(res[r], rs, mx_off(r, 4), 0, decltype(aux)::value);
+            }
+        }
+    };
+    if (a.store_sc1) store(std::integral_constant<int, kAuxSC1NT>());
+    else store(std::integral_constant<int, kAuxNT>());
+}
+
+// One tile per one-wave block; block 0 also does the scalar head and tail.
+// All k loads (and acc's) are issued before the first combine (uniform
+// branches on k only); the fast fold without the NaN fix-ups, then the screen
+// on the inputs as loaded and the x86 refold of the runs that hold an Inf or
+// NaN.  mx_fold is force-inlined and x[] is indexed by constants only: with
+// the fold's runtime-k branches in a callee the compiler may keep x[] as an
+// aggregate in scratch (fan_fold's note; tests/test_kernel_resources.py).
+template <typename ST, typename DT, unsigned V, int RUNS, int KMAX>
+__global__ __launch_bounds__(kMixedBlock) void mixed_kernel(MXArgs a) {
+    using SS = typename Tr<ST>::S;
+    constexpr bool WIDE = std::is_same<DT, float>::value;
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.ngroups * 8, [&](uint64_t i) { mixed_elem<ST, DT, V>(a, i); });
+    uint64_t first;
+    uint32_t ne;
+    mx_tile_of<RUNS>(a, blockIdx.x, first, ne);
+    if (ne == 0) return;
+    const int k = a.k;
+    const bool has_acc = WIDE && a.acc != nullptr;
+
+    const void* in[KMAX];
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+        in[i] = a.in[i];
+        asm volatile("" ::"s"(in[i]));
+    }
+    typename MxRun<ST>::type x[RUNS][KMAX] = {};  // defined in every slot: the fold's k is opaque (below)
+#pragma unroll
+    for (int i = 0; i < KMAX; i++) {
+        if (i < k) {
+            const __amdgpu_buffer_rsrc_t rs = tile_rsrc(in[i], first * sizeof(SS), ne * (uint32_t)sizeof(SS));
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) x[r][i] = mx_load<ST>(rs, mx_off(r, sizeof(SS)));
+        }
+    }
+    u32x4 xa[RUNS];
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) xa[r] = u32x4{0u, 0u, 0u, 0u};
+    if constexpr (WIDE) {
+        if (has_acc) {
+            const __amdgpu_buffer_rsrc_t rs = tile_rsrc(a.acc, first * 4, ne * 4u);
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) xa[r] = __builtin_amdgcn_raw_buffer_load_b128(rs, mx_off(r, 4), 0, kAuxNT);
+        }
+    }
+    // The fold's branches test a copy of k the compiler cannot relate to the
+    // loads' k, and x[] is defined in every slot: the branches of the loads
+    // cannot be threaded through those of the fold (one path per k, all of x[]
+    // merged where the paths meet), so every load is issued before the first
+    // combine whatever the compiler makes of the fold.  Written against the
+    // one-run layout's registers (238 to 492 VGPRs, each load next to its use),
+    // which it did not cure; with two runs it costs at most one VGPR.
+    int kf = k;
+    asm volatile("" : "+s"(kf));
+
+    typename MxRun<DT>::type res[RUNS];
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) {
+        const uint64_t e0 = first + (uint64_t)(r * kMixedBlock + threadIdx.x) * 4u;
+        res[r] = mx_fold<ST, DT, V, false, KMAX>(x[r], kf, has_acc, xa[r], e0, a.trunc_from);
+        bool hit = WIDE && mx_inf_nan<float>(xa[r]);
+#pragma unroll
+        for (int i = 0; i < KMAX; i++)
+            if (i < kf) hit |= mx_inf_nan<ST>(x[r][i]);
+        if (__builtin_expect(hit, 0)) res[r] = mx_fold<ST, DT, V, true, KMAX>(x[r], kf, has_acc, xa[r], e0, a.trunc_from);
+    }
+    mx_store<DT, RUNS>(a, a.m, res, first, ne);
+}
+
+// The grid-stride form (launches under mi_set_max_blocks) and the element
+// loop (`scalar_only`).  The blocks stride over the same tiles, addressed as
+// above; the fold is a runtime loop over the inputs, acc's load first, the
+// next input's load in flight while one is combined, every step with the x86
+// NaN bits (bcast_stride_kernel's shape), so a lane still has every load back
+// before its first store.  Same bits as mixed_kernel.
+template <typename ST, typename DT, unsigned V, int RUNS>
+__global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
+    using SS = typename Tr<ST>::S;
+    constexpr bool WIDE = std::is_same<DT, float>::value;
+    if (a.scalar_only) {
+        for (uint64_t i = (uint64_t)blockIdx.x * kMixedBlock + threadIdx.x; i < a.count;
+             i += (uint64_t)gridDim.x * kMixedBlock)
+            mixed_elem<ST, DT, V>(a, i);
+        return;
+    }
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.ngroups * 8, [&](uint64_t i) { mixed_elem<ST, DT, V>(a, i); });
+    const int k = a.k;
+    const bool has_acc = WIDE && a.acc != nullptr;
+    for (uint64_t tile = blockIdx.x; tile * mixed_tile_elems<RUNS>() < a.ngroups * 8; tile += gridDim.x) {
+        uint64_t first;
+        uint32_t ne;
+        mx_tile_of<RUNS>(a, tile, first, ne);
+        typename MxRun<ST>::type cur[RUNS], nxt[RUNS];
+        const auto load = [&](int i, typename MxRun<ST>::type (&x)[RUNS]) {
+            const __amdgpu_buffer_rsrc_t rs = tile_rsrc(a.in[i], first * sizeof(SS), ne * (uint32_t)sizeof(SS));
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) x[r] = mx_load<ST>(rs, mx_off(r, sizeof(SS)));
+        };
+        float s[RUNS][4], c[4];
+        if constexpr (WIDE) {
+            if (has_acc) {
+                const __amdgpu_buffer_rsrc_t rs = tile_rsrc(a.acc, first * 4, ne * 4u);
+#pragma unroll
+                for (int r = 0; r < RUNS; r++) {
+                    const u32x4 xa = __builtin_amdgcn_raw_buffer_load_b128(rs, mx_off(r, 4), 0, kAuxNT);
+#pragma unroll
+                    for (int e = 0; e < 4; e++) s[r][e] = __uint_as_float(xa[e]);
+                }
+            }
+        }
+        load(0, cur);
+        for (int i = 0; i < k; i++) {
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) nxt[r] = cur[r];
+            if (i + 1 < k) load(i + 1, nxt);
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) {
+                mx_widen<ST, true>(cur[r], c);
+#pragma unroll
+                for (int e = 0; e < 4; e++) s[r][e] = (i == 0 && !has_acc) ? c[e] : step<float, OP_SUM, 0u, true>(c[e], s[r][e]);
+                cur[r] = nxt[r];
+            }
+        }
+        typename MxRun<DT>::type res[RUNS];
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) {
+            if constexpr (WIDE) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) res[r][e] = __float_as_uint(s[r][e]);
+            } else {
+                const uint64_t e0 = first + (uint64_t)(r * kMixedBlock + threadIdx.x) * 4u;
+                uint32_t h[4];
+#pragma unroll
+                for (int e = 0; e < 4; e++) h[e] = finish<DT, V, true>(s[r][e], e0 + e, a.trunc_from);
+                res[r].x = h[0] | (h[1] << 16);
+                res[r].y = h[2] | (h[3] << 16);
+            }
+        }
+        mx_store<DT, RUNS>(a, a.m, res, first, ne);
+    }
+}
+
 // Byte copy with optional non-temporal stores (ccl_comp_copy), on the
 // destination's 16-byte grid: block 0 copies the < 16-byte head and tail byte
 // by byte, the body moves 16-byte vectors.  The source may sit at any byte

@@ -53,4 +53,50 @@ inline VecGrid plan_vec_grid(size_t es, size_t count, const void* const* outs, i
     return g;
 }
 
+// The plan of a launch whose inputs and outputs differ in element size
+// (mi_reduce_bcast_mixed; es_in, es_out = 2, 4 or 4, 2): launch_convert's.
+// count = head + 8 * ngroups + tail: a scalar head up to the outputs' first
+// 16-byte boundary (< 16 / es_out elements), a body of groups of 8 elements
+// (16 bytes on the 16-bit side, 32 on the fp32 side), a scalar tail (< 8).
+// The body's stores, 4 elements wide, are aligned to their width at every
+// group.  !vec: the element loop takes the whole count.
+struct MixedGrid {
+    bool vec;
+    size_t head;
+    uint64_t ngroups;
+    size_t tail;
+};
+
+// The element loop is taken when the outputs sit at differing misalignments
+// mod 16, when an operand is not aligned to its element size (`acc`, fp32 or
+// null, included), or, with `unaligned_ok` off, when an input or `acc` is off
+// the grid: its element `head` is not on a 16-byte boundary.  Otherwise inputs
+// may sit at any element-aligned offset, read with unaligned loads.
+inline MixedGrid plan_mixed_grid(size_t es_in, size_t es_out, size_t count, const void* const* outs, int m,
+                                 const void* const* ins, int k, const void* acc, bool unaligned_ok) {
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(outs[0]), mis = o0 & 15u;
+    bool elem = (mis % es_out) == 0, same_out = true;
+    for (int i = 1; i < m; i++) same_out = same_out && (reinterpret_cast<uintptr_t>(outs[i]) & 15u) == mis;
+    MixedGrid g = {false, 0, 0, 0};
+    if (!same_out || !elem) return g;
+    const size_t head = grid_head(o0, es_out, count);
+    bool on_grid = true;
+    for (int i = 0; i < k; i++) {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(ins[i]);
+        elem = elem && (p % es_in) == 0;
+        on_grid = on_grid && ((p + head * es_in) & 15u) == 0;
+    }
+    if (acc) {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(acc);
+        elem = elem && (p % 4) == 0;
+        on_grid = on_grid && ((p + head * 4) & 15u) == 0;
+    }
+    if (!elem || !(on_grid || unaligned_ok)) return g;
+    g.vec = true;
+    g.head = head;
+    g.ngroups = (count - head) / 8;
+    g.tail = count - head - (size_t)g.ngroups * 8;
+    return g;
+}
+
 }  // namespace mi
