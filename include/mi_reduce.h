@@ -265,13 +265,65 @@ int mi_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, 
  * size, and, under mi_set_unaligned_vectors(0), inputs off the outputs' grid
  * take the element loop (same bits).
  *   Not provided: a _sync, staged or pageable form, a request form, a host-CPU
- * path, a drop-in C++ symbol or a patch under integration/, a scale, ops
- * other than sum, fp64 and integer types, peer-GPU destinations (untested, as
- * for mi_reduce_bcast).  mi_version() is unchanged: the symbol's presence is
- * how a caller detects the entry point.                                     */
+ * path, a drop-in C++ symbol or a patch under integration/, ops other than
+ * sum, fp64 and integer types, peer-GPU destinations (untested, as for
+ * mi_reduce_bcast).  A scale is mi_reduce_bcast_mixed_scaled, below.
+ * mi_version() is unchanged: the symbol's presence is how a caller detects
+ * the entry point.                                                          */
 int mi_reduce_bcast_mixed(const void* const* inputs, int k, int in_dtype,
                           const void* acc, void* const* outs, int m, int out_dtype,
                           size_t count, int op, unsigned flags, void* stream);
+
+/* mi_reduce_bcast_mixed with one multiply: the mean over ranks (scale = 1/N)
+ * or a loss-scale factor across precisions, main_grad (fp32) += (1/N) * sum of
+ * the bf16 / fp16 wire gradients, or the mean of fp32 partials written once as
+ * bf16 / fp16, in one pass.  Everything mi_reduce_bcast_mixed documents holds
+ * unchanged: the four dtype pairs, sum only, acc only when widening and
+ * counting against MI_MAX_INPUTS, the refusals and their order (the dtype
+ * pair first), the overlap rules (acc may be exactly one output), device or
+ * device-visible pinned pointers, asynchronous on `stream`, one kernel node in
+ * a HIP graph, the element loop's conditions, count == 0 returning 0 after
+ * the checks.
+ *   Let s = (float)scale (round to nearest even).  MI_E_INVALID, before any
+ * HIP call and after the list checks (as mi_reduce_bcast_scaled): a scale that
+ * is NaN or infinite, an s that is zero or infinite (1e-60, 1e300).  Every
+ * output holds exactly the bytes of these compositions of existing calls:
+ *   Widening, acc == NULL.  S = what mi_reduce_bcast_mixed(inputs, acc = NULL)
+ * stores; outs[i][e] = S[e] where S[e] is a NaN, else S[e] * s: that is
+ * mi_reduce_bcast_scaled({S}, k = 1, fp32, scale).  At scale 1 it is the
+ * unscaled call's bytes.
+ *   Widening, acc != NULL.  P = the result above, the scaled sum of the wire
+ * inputs alone; outs[i] = mi_reduce_multi({acc, P}, fp32, sum): one add with
+ * acc as the accumulator (x86's first source: of two NaNs acc's comes back)
+ * and P in the `in` role.  That is acc + s * sum(c_j), the averaged gradient
+ * added to the main gradient; it is not s * (acc + sum(c_j)), and it is not
+ * the unscaled call's left fold {acc, c_0, ...} either: at scale 1 the two
+ * differ in the last bit where the order of the additions matters (968 of
+ * 12293 elements of the bf16 test inputs).  The product is rounded to fp32
+ * before the add: the multiply and the add are never fused into one
+ * operation (the kernels keep the pair out of the compiler's contraction).
+ *   Narrowing.  F = mi_reduce_multi(inputs, fp32, sum); P[e] = F[e] where
+ * F[e] is a NaN, else F[e] * s (mi_reduce_bcast_scaled in fp32); outs[i] =
+ * mi_convert(P, fp32 -> out_dtype, flags): bf16 truncation, MI_F_BF16_RNE, or
+ * MI_F_BF16_RNE | MI_F_BF16_TAIL_TRUNC16; fp16 round to nearest even.  One
+ * rounding to storage, of the product, where a second pass over a stored sum
+ * rounds twice.  At scale 1 it is the unscaled call's bytes.
+ *   The multiply is one IEEE-754 fp32 multiply, round to nearest even,
+ * denormals kept; a NaN never reaches the multiplier.
+ *   Against the sequences it replaces it moves 2k + 4m (+ 4 with acc) and
+ * 4k + 2m bytes per element in one dispatch: widening, the unscaled call and
+ * a scaling pass per output move 2k + 12m; with acc, the unscaled call into a
+ * scratch buffer, a scaling pass and an fp32 mi_reduce_bcast move 2k + 20 + 4m
+ * in three dispatches; narrowing, mi_reduce_bcast_scaled into an fp32 scratch
+ * buffer and m mi_convert calls move 4k + 4 + 6m.
+ *   Not provided: a _sync, staged or pageable form, a request form, a host-CPU
+ * path, a drop-in C++ symbol or a patch under integration/, ops other than
+ * sum, fp64 and integer types, peer-GPU destinations.  mi_version() is
+ * unchanged: the symbol's presence is how a caller detects the entry point. */
+int mi_reduce_bcast_mixed_scaled(const void* const* inputs, int k, int in_dtype,
+                                 const void* acc, void* const* outs, int m, int out_dtype,
+                                 size_t count, int op, unsigned flags, double scale,
+                                 void* stream);
 
 /* n independent mi_reduce calls in one dispatch: descs[i].inout =
  * op(descs[i].in, descs[i].inout) over descs[i].count elements, all with one
@@ -529,7 +581,9 @@ int mi_get_residency(int device, int k, int* waves_per_cu, unsigned* lds_bytes);
  * (2, 1), which takes the 2-input kernel's plan (k = 2 above).
  * mi_reduce_bcast_mixed plans likewise, by s = min(k + acc + m - 1, 16) with
  * acc = 1 when an accumulator is given, and by the 2-input kernel's plan for
- * two loads and one store per lane (k + acc = 2, m = 1).                     */
+ * two loads and one store per lane (k + acc = 2, m = 1);
+ * mi_reduce_bcast_mixed_scaled takes that plan as it is (adopted, its own
+ * residencies were not swept).                                              */
 int mi_set_residency(int k, int waves_per_cu);
 /* Store policy of mi_reduce_bcast's vector stores (tuning knob): 1 (default)
  * = sc1 + nt, as the 2-input kernel stores (the line leaves L2 as it is

@@ -23,6 +23,7 @@ from .comp import (  # noqa: F401
     reduce,
     reduce_bcast,
     reduce_bcast_mixed,
+    reduce_bcast_mixed_scaled,
     reduce_bcast_scaled,
     reduce_multi,
     reduce_out,

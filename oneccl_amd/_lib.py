@@ -46,6 +46,8 @@ MI_API = [
                                        c_uint, c_double, c_void_p]),
     ("mi_reduce_bcast_mixed", c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, POINTER(c_void_p), c_int, c_int,
                                       c_size_t, c_int, c_uint, c_void_p]),
+    ("mi_reduce_bcast_mixed_scaled", c_int, [POINTER(c_void_p), c_int, c_int, c_void_p, POINTER(c_void_p), c_int,
+                                             c_int, c_size_t, c_int, c_uint, c_double, c_void_p]),
     ("mi_reduce_batch", c_int, [POINTER(MiReduceDesc), c_int, c_int, c_int, c_uint, c_void_p]),
     ("mi_reduce_sync", c_int, [c_void_p, c_void_p, c_size_t, c_int, c_int, c_uint, c_int]),
     ("mi_reduce_multi_sync", c_int, [POINTER(c_void_p), c_int, c_void_p, c_size_t, c_int, c_int, c_uint, c_int]),

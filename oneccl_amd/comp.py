@@ -204,22 +204,17 @@ def reduce_bcast_scaled(inputs: Sequence, outs: Sequence, scale: float, flags: O
           "mi_reduce_bcast_scaled")
 
 
-def reduce_bcast_mixed(inputs: Sequence, outs: Sequence, acc=None, flags: Optional[int] = None,
-                       stream=None) -> None:
-    """Every tensor of `outs` = the fp32 sum over `inputs` (on top of the fp32
-    tensor `acc`, if given), stored in the outputs' precision, in one pass
-    (mi_reduce_bcast_mixed).  bf16 or fp16 inputs with fp32 outputs, or fp32
-    inputs with bf16 or fp16 outputs (no `acc` then); the dtypes are the
-    tensors'.  `acc` may be one of the outputs; no output may overlap an input.
-    flags=None: reference_flags of the 16-bit dtype."""
+def _mixed_args(inputs: Sequence, outs: Sequence, acc, flags: Optional[int], what: str):
+    """The tensor checks reduce_bcast_mixed and reduce_bcast_mixed_scaled
+    share: (inputs, outs, in dtype, out dtype, count, flags)."""
     inputs, outs = list(inputs), list(outs)
     if not inputs or not outs:
-        raise ValueError("reduce_bcast_mixed needs at least one input and one output")
+        raise ValueError(f"{what} needs at least one input and one output")
     t0, o0 = inputs[0], outs[0]
-    for group, first, what in ((inputs, t0, "inputs"), (outs, o0, "outputs")):
+    for group, first, side in ((inputs, t0, "inputs"), (outs, o0, "outputs")):
         for t in group:
             if t.dtype != first.dtype:
-                raise TypeError(f"all {what} must have one dtype ({t.dtype} against {first.dtype})")
+                raise TypeError(f"all {side} must have one dtype ({t.dtype} against {first.dtype})")
     idt, odt = _torch_ccl_dtype(t0), _torch_ccl_dtype(o0)
     lp = (datatype.bfloat16, datatype.float16)
     if not ((idt in lp and odt == datatype.float32) or (idt == datatype.float32 and odt in lp)):
@@ -241,10 +236,38 @@ def reduce_bcast_mixed(inputs: Sequence, outs: Sequence, acc=None, flags: Option
     if not t0.is_cuda:
         raise ValueError("device entry points take device tensors")
     f = reference_flags(idt if idt in lp else odt) if flags is None else flags
+    return inputs, outs, idt, odt, t0.numel(), f
+
+
+def reduce_bcast_mixed(inputs: Sequence, outs: Sequence, acc=None, flags: Optional[int] = None,
+                       stream=None) -> None:
+    """Every tensor of `outs` = the fp32 sum over `inputs` (on top of the fp32
+    tensor `acc`, if given), stored in the outputs' precision, in one pass
+    (mi_reduce_bcast_mixed).  bf16 or fp16 inputs with fp32 outputs, or fp32
+    inputs with bf16 or fp16 outputs (no `acc` then); the dtypes are the
+    tensors'.  `acc` may be one of the outputs; no output may overlap an input.
+    flags=None: reference_flags of the 16-bit dtype."""
+    inputs, outs, idt, odt, count, f = _mixed_args(inputs, outs, acc, flags, "reduce_bcast_mixed")
     check(mi().mi_reduce_bcast_mixed(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), int(idt),
                                      acc.data_ptr() if acc is not None else None,
-                                     void_ptr_array([t.data_ptr() for t in outs]), len(outs), int(odt), t0.numel(),
+                                     void_ptr_array([t.data_ptr() for t in outs]), len(outs), int(odt), count,
                                      int(reduction.sum), f, _stream_handle(stream)), "mi_reduce_bcast_mixed")
+
+
+def reduce_bcast_mixed_scaled(inputs: Sequence, outs: Sequence, scale: float, acc=None,
+                              flags: Optional[int] = None, stream=None) -> None:
+    """reduce_bcast_mixed with one fp32 multiply (mi_reduce_bcast_mixed_scaled;
+    scale = 1 / len(inputs) is the mean): every tensor of `outs` = the fp32 sum
+    over `inputs` times `scale`, stored in the outputs' precision with one
+    rounding; with `acc`, acc + scale * sum (the product rounded to fp32, then
+    one add), which is main_grad += the averaged wire gradients when `acc` is
+    one of the outputs.  dtypes, aliasing and flags as reduce_bcast_mixed."""
+    inputs, outs, idt, odt, count, f = _mixed_args(inputs, outs, acc, flags, "reduce_bcast_mixed_scaled")
+    check(mi().mi_reduce_bcast_mixed_scaled(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), int(idt),
+                                            acc.data_ptr() if acc is not None else None,
+                                            void_ptr_array([t.data_ptr() for t in outs]), len(outs), int(odt), count,
+                                            int(reduction.sum), f, float(scale), _stream_handle(stream)),
+          "mi_reduce_bcast_mixed_scaled")
 
 
 # ---- the drop-in shim (synchronous, host or device pointers) ------------

@@ -924,6 +924,34 @@ hipError_t launch_mixed(unsigned stride_blocks, unsigned tiles, hipStream_t s, c
     return hipGetLastError();
 }
 
+// mi_reduce_bcast_mixed_scaled: launch_mixed's routing onto the kernels with a multiplier.
+typedef hipError_t (*LaunchMxScFn)(unsigned stride_blocks, unsigned tiles, hipStream_t, const MXArgs&, const ScaleArg&,
+                                   unsigned lds);
+
+template <typename ST, typename DT, unsigned V, int RUNS>
+hipError_t launch_mixed_scaled(unsigned stride_blocks, unsigned tiles, hipStream_t s, const MXArgs& a,
+                               const ScaleArg& sc, unsigned lds) {
+    if (stride_blocks)
+        hipLaunchKernelGGL((mixed_scaled_stride_kernel<ST, DT, V, RUNS>), dim3(stride_blocks), dim3(kMixedBlock), 0, s, a,
+                           sc);
+    else if (a.k <= 8)
+        hipLaunchKernelGGL((mixed_scaled_kernel<ST, DT, V, RUNS, 8>), dim3(tiles), dim3(kMixedBlock), lds, s, a, sc);
+    else
+        hipLaunchKernelGGL((mixed_scaled_kernel<ST, DT, V, RUNS, kMaxInputs>), dim3(tiles), dim3(kMixedBlock), lds, s, a,
+                           sc);
+    return hipGetLastError();
+}
+
+LaunchMxScFn pick_mixed_scaled(int idt, int odt, unsigned v) {
+    constexpr int RUNS = kMixedRuns;
+    if (idt == MI_BFLOAT16) return &launch_mixed_scaled<bf16_tag, float, 0u, RUNS>;
+    if (idt == MI_FLOAT16) return &launch_mixed_scaled<fp16_tag, float, 0u, RUNS>;
+    if (odt == MI_FLOAT16) return &launch_mixed_scaled<float, fp16_tag, 0u, RUNS>;
+    if (!(v & V_BF16_RNE)) return &launch_mixed_scaled<float, bf16_tag, 0u, RUNS>;
+    return (v & V_TAIL_TRUNC) ? &launch_mixed_scaled<float, bf16_tag, V_BF16_RNE | V_TAIL_TRUNC, RUNS>
+                              : &launch_mixed_scaled<float, bf16_tag, V_BF16_RNE, RUNS>;
+}
+
 LaunchMxFn pick_mixed(int idt, int odt, unsigned v) {
     constexpr int RUNS = kMixedRuns;
     if (idt == MI_BFLOAT16) return &launch_mixed<bf16_tag, float, 0u, RUNS>;
@@ -990,8 +1018,11 @@ int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void*
     return 0;
 }
 
-int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m,
-                              int odt, size_t count, int op, unsigned flags, hipStream_t stream) {
+// The checks mi_reduce_bcast_mixed and mi_reduce_bcast_mixed_scaled make before
+// they look at an operand, in the documented order: the dtype pair, the op,
+// acc against the direction, k and m, the lists.
+int check_mixed_lists(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m, int odt,
+                      int op, bool* narrowing_out) {
     const bool widening = (idt == MI_BFLOAT16 || idt == MI_FLOAT16) && odt == MI_FLOAT32;
     const bool narrowing = idt == MI_FLOAT32 && (odt == MI_BFLOAT16 || odt == MI_FLOAT16);
     if (!widening && !narrowing)
@@ -1007,10 +1038,18 @@ int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const v
     if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
     if (!inputs) return fail(MI_E_INVALID, "null input list");
     if (!outs) return fail(MI_E_INVALID, "null output list");
-    const size_t es_in = dtype_size(idt), es_out = dtype_size(odt);
-    if (int rc = check_mixed_args(inputs, k, es_in, acc, outs, m, es_out, count)) return rc;
-    if (count == 0) return 0;
+    *narrowing_out = narrowing;
+    return 0;
+}
 
+// What the two calls share once their arguments have passed: the visibility
+// checks, the variant, the outputs' grid, the residency plan and the grid-cap
+// routing.  launch(v, stride_blocks, tiles, args, lds) starts the kernel of
+// variant bits v (launch_mixed's convention).
+template <typename Launch>
+int issue_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m, int odt,
+                size_t count, int op, unsigned flags, bool narrowing, hipStream_t stream, Launch&& launch) {
+    const size_t es_in = dtype_size(idt), es_out = dtype_size(odt);
     for (int i = 0; i < k; i++)
         if (int rc = require_gpu_visible(inputs[i], count * es_in)) return rc;
     if (acc)
@@ -1020,7 +1059,6 @@ int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const v
 
     // the variant bits that change a bit: the narrowing conversion's (canon_flags)
     const unsigned v = narrowing ? (canon_flags(odt, op, flags | V_ACC_FP32, k) & (V_BF16_RNE | V_TAIL_TRUNC)) : 0u;
-    const LaunchMxFn fn = pick_mixed(idt, odt, v);
 
     const MixedGrid g = plan_mixed_grid(es_in, es_out, count, outs, m, inputs, k, acc, unaligned_vectors() != 0);
     MXArgs a;
@@ -1049,17 +1087,49 @@ int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const v
         // fan-out's 16 waves and at 0.314 at 21; fp32 to bf16 the same within 1 %
         // at 12, 16 and 21.  At the other shapes measured ((8, 1), (8, 1) with
         // acc, (2, 2), (8, 8)) the plan was the fastest or within 2 % of it
-        // (tools/mixed_sweep.py --residency, profiles/reduce_mixed/).
+        // (tools/mixed_sweep.py --residency, profiles/reduce_mixed/).  Those
+        // figures are the unscaled call's; the scaled call adopts the plan
+        // unmeasured (its streams are the same).
         const int ks = k + (acc ? 1 : 0);
         const int waves = (ks == 2 && m == 1) ? planned_waves(2) : bcast_planned_waves(ks, m);
-        e = fn(0u, (unsigned)tiles, stream, a, wave_cap_lds(stream, waves));
+        e = launch(v, 0u, (unsigned)tiles, a, wave_cap_lds(stream, waves));
     } else {
         uint64_t blocks = g.vec ? tiles : std::min<uint64_t>((count + kMixedBlock - 1) / kMixedBlock, 8192);
         if (g.vec && cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
-        e = fn((unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull), 0u, stream, a, 0u);
+        e = launch(v, (unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull), 0u, a, 0u);
     }
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return 0;
+}
+
+int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m,
+                              int odt, size_t count, int op, unsigned flags, hipStream_t stream) {
+    bool narrowing;
+    if (int rc = check_mixed_lists(inputs, k, idt, acc, outs, m, odt, op, &narrowing)) return rc;
+    if (int rc = check_mixed_args(inputs, k, dtype_size(idt), acc, outs, m, dtype_size(odt), count)) return rc;
+    if (count == 0) return 0;
+    return issue_mixed(inputs, k, idt, acc, outs, m, odt, count, op, flags, narrowing, stream,
+                       [&](unsigned v, unsigned stride_blocks, unsigned tiles, const MXArgs& a, unsigned lds) {
+                           return pick_mixed(idt, odt, v)(stride_blocks, tiles, stream, a, lds);
+                       });
+}
+
+// mi_reduce_bcast_mixed_scaled: the same call with the multiplier of
+// mi_reduce_bcast_scaled in the float compute type (check_scale with an fp32
+// dtype), refused after the list checks and before the operands', as there.
+int launch_reduce_bcast_mixed_scaled(const void* const* inputs, int k, int idt, const void* acc, void* const* outs,
+                                     int m, int odt, size_t count, int op, unsigned flags, double scale,
+                                     hipStream_t stream) {
+    bool narrowing;
+    if (int rc = check_mixed_lists(inputs, k, idt, acc, outs, m, odt, op, &narrowing)) return rc;
+    ScaleArg sc;
+    if (int rc = check_scale(MI_FLOAT32, scale, &sc)) return rc;
+    if (int rc = check_mixed_args(inputs, k, dtype_size(idt), acc, outs, m, dtype_size(odt), count)) return rc;
+    if (count == 0) return 0;
+    return issue_mixed(inputs, k, idt, acc, outs, m, odt, count, op, flags, narrowing, stream,
+                       [&](unsigned v, unsigned stride_blocks, unsigned tiles, const MXArgs& a, unsigned lds) {
+                           return pick_mixed_scaled(idt, odt, v)(stride_blocks, tiles, stream, a, sc, lds);
+                       });
 }
 
 // ---------------------------------------------------------------------------
@@ -2347,6 +2417,13 @@ int mi_reduce_bcast_mixed(const void* const* inputs, int k, int in_dtype, const 
                           int out_dtype, size_t count, int op, unsigned flags, void* stream) {
     return launch_reduce_bcast_mixed(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags,
                                      (hipStream_t)stream);
+}
+
+int mi_reduce_bcast_mixed_scaled(const void* const* inputs, int k, int in_dtype, const void* acc, void* const* outs,
+                                 int m, int out_dtype, size_t count, int op, unsigned flags, double scale,
+                                 void* stream) {
+    return launch_reduce_bcast_mixed_scaled(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags, scale,
+                                            (hipStream_t)stream);
 }
 
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op, unsigned flags,

@@ -1398,6 +1398,12 @@ __global__ __launch_bounds__(B) void convert_kernel(CArgs a) {
 // back before its first store; `acc` may be exactly one output (both fp32, so
 // it sits on the outputs' grid and a lane loads exactly the bytes it later
 // stores): mi_reduce_bcast's in-place argument.
+//   mi_reduce_bcast_mixed_scaled runs the same bodies with a multiplier (the SC
+// parameter, as the scaled fan-out): kernels of their own, MXArgs unchanged.
+// The inputs are folded alone, their sum is scaled once and acc is added last
+// (mx_scaled, mx_scaled_onto); the multiply sits after the last combine of the
+// inputs and acc's load is issued with theirs, so the order of loads and
+// stores, and with it the in-place argument, is unchanged.
 // ---------------------------------------------------------------------------
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
@@ -1459,14 +1465,52 @@ __device__ __forceinline__ bool mx_inf_nan(const typename MxRun<T>::type& x) {
                                   inf_nan_word<float>(x.w));
 }
 
+// mi_reduce_bcast_mixed_scaled: the fp32 sum of the inputs alone times the
+// multiplier, one IEEE multiply rounded to fp32 (finish_scaled's rule: a NaN
+// sum is kept as it is and never reaches the multiplier, whose NaN choice is
+// the hardware's; X = false leaves the select out, the caller refolds every
+// row its Inf/NaN screen hits).
+template <bool X>
+__device__ __forceinline__ float mx_scaled(float sum, float s) {
+#pragma clang fp contract(off)
+    const float p = sum * s;
+    if constexpr (X) return (sum != sum) ? sum : p;
+    else return p;
+}
+// That product added to the accumulator: acc + (float)(sum * s), one x86-rule
+// add with acc as first source (mi_reduce_multi({acc, P}, fp32, sum)).  The
+// product is rounded before the add: with contraction on (the build's default)
+// the compiler makes the pair one v_fmac_f32, which rounds once and differs in
+// the last bit (in 2630 of 12259 finite elements of the bf16 test inputs at
+// scale 1/3), so both operations stand in this one body with contraction off.
+template <bool X>
+__device__ __forceinline__ float mx_scaled_onto(float sum, float s, float acc) {
+#pragma clang fp contract(off)
+    const float p = mx_scaled<X>(sum, s);
+    const float r = acc + p;
+    if constexpr (X) return x86_nan_first(r, acc, p);
+    else return r;
+}
+
 // The fold of one run of 4 elements across the loaded inputs (and acc), and
-// its final conversion.  e0: the run's first element index.
-template <typename ST, typename DT, unsigned V, bool X, int KMAX>
+// its final conversion.  e0: the run's first element index.  Under a
+// multiplier (SC = ScaleArg) the inputs are folded alone, the sum is scaled
+// and acc is added last (mx_scaled_onto): acc + s * sum, not s * (acc + sum).
+//   The X = false form under a multiplier is still exact on every run the
+// callers' screen (an all-ones exponent in an input or in acc as loaded) does
+// not hit: s is finite and not zero, so the product of a finite sum is finite
+// or, on overflow, an Inf; a sum of finite inputs is finite or an Inf of one
+// sign (no Inf - Inf without an Inf input); and acc is finite there, so the
+// last add has at most one Inf operand.  No NaN can arise, and without a NaN
+// the fix-ups change nothing.
+template <typename ST, typename DT, unsigned V, bool X, int KMAX, typename SC = NoScale>
 __device__ __forceinline__ typename MxRun<DT>::type mx_fold(const typename MxRun<ST>::type (&x)[KMAX], int k,
                                                             bool has_acc, u32x4 xa, uint64_t e0,
-                                                            uint64_t trunc_from) {
+                                                            uint64_t trunc_from, const SC& sc = SC()) {
+    constexpr bool SCALED = !std::is_same<SC, NoScale>::value;
+    const bool from_acc = SCALED ? false : has_acc;  // the unscaled fold starts from acc
     float s[4], c[4];
-    if (has_acc) {
+    if (from_acc) {
 #pragma unroll
         for (int e = 0; e < 4; e++) s[e] = __uint_as_float(xa[e]);
     }
@@ -1474,13 +1518,23 @@ __device__ __forceinline__ typename MxRun<DT>::type mx_fold(const typename MxRun
     for (int i = 0; i < KMAX; i++) {
         if (i < k) {
             mx_widen<ST, X>(x[i], c);
-            if (i == 0 && !has_acc) {
+            if (i == 0 && !from_acc) {
 #pragma unroll
                 for (int e = 0; e < 4; e++) s[e] = c[e];
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; e++) s[e] = step<float, OP_SUM, 0u, X>(c[e], s[e]);
             }
+        }
+    }
+    if constexpr (SCALED) {
+        const float f = sc.template as<float>();
+        if (has_acc) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) s[e] = mx_scaled_onto<X>(s[e], f, __uint_as_float(xa[e]));
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) s[e] = mx_scaled<X>(s[e], f);
         }
     }
     typename MxRun<DT>::type r;
@@ -1499,10 +1553,11 @@ __device__ __forceinline__ typename MxRun<DT>::type mx_fold(const typename MxRun
 
 // Element `idx` on the scalar path (head, tail, element loop), stored to every
 // output.
-template <typename ST, typename DT, unsigned V>
-__device__ __forceinline__ void mixed_elem(const MXArgs& a, uint64_t idx) {
+template <typename ST, typename DT, unsigned V, typename SC = NoScale>
+__device__ __forceinline__ void mixed_elem(const MXArgs& a, uint64_t idx, const SC& sc = SC()) {
     using SS = typename Tr<ST>::S;
     using DS = typename Tr<DT>::S;
+    constexpr bool SCALED = !std::is_same<SC, NoScale>::value;
     const auto c = [&](int j) -> float {
         if constexpr (sizeof(SS) == 2)
             return convert_elem<ST, float, 0u, true>(static_cast<const SS*>(a.in[j])[idx], 0, 0);
@@ -1511,9 +1566,13 @@ __device__ __forceinline__ void mixed_elem(const MXArgs& a, uint64_t idx) {
     };
     float s;
     int j = 0;
-    if (a.acc) s = static_cast<const float*>(a.acc)[idx];
+    if (!SCALED && a.acc) s = static_cast<const float*>(a.acc)[idx];
     else s = c(j++);
     for (; j < a.k; j++) s = step<float, OP_SUM, 0u, true>(c(j), s);
+    if constexpr (SCALED) {  // the inputs' sum alone, scaled, then onto acc (mx_fold)
+        const float f = sc.template as<float>();
+        s = a.acc ? mx_scaled_onto<true>(s, f, static_cast<const float*>(a.acc)[idx]) : mx_scaled<true>(s, f);
+    }
     DS r;
     if constexpr (std::is_same<DT, float>::value) r = s;
     else r = finish<DT, V, true>(s, idx, a.trunc_from);
@@ -1566,11 +1625,11 @@ __device__ __forceinline__ void mx_store(const MXArgs& a, int m, const typename 
 // NaN.  mx_fold is force-inlined and x[] is indexed by constants only: with
 // the fold's runtime-k branches in a callee the compiler may keep x[] as an
 // aggregate in scratch (fan_fold's note; tests/test_kernel_resources.py).
-template <typename ST, typename DT, unsigned V, int RUNS, int KMAX>
-__global__ __launch_bounds__(kMixedBlock) void mixed_kernel(MXArgs a) {
+template <typename ST, typename DT, unsigned V, int RUNS, int KMAX, typename SC>
+__device__ __forceinline__ void mixed_tile(const MXArgs& a, const SC& sc) {
     using SS = typename Tr<ST>::S;
     constexpr bool WIDE = std::is_same<DT, float>::value;
-    head_tail(blockIdx.x, a.head, a.tail, a.head + a.ngroups * 8, [&](uint64_t i) { mixed_elem<ST, DT, V>(a, i); });
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.ngroups * 8, [&](uint64_t i) { mixed_elem<ST, DT, V>(a, i, sc); });
     uint64_t first;
     uint32_t ne;
     mx_tile_of<RUNS>(a, blockIdx.x, first, ne);
@@ -1617,14 +1676,27 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_kernel(MXArgs a) {
 #pragma unroll
     for (int r = 0; r < RUNS; r++) {
         const uint64_t e0 = first + (uint64_t)(r * kMixedBlock + threadIdx.x) * 4u;
-        res[r] = mx_fold<ST, DT, V, false, KMAX>(x[r], kf, has_acc, xa[r], e0, a.trunc_from);
+        res[r] = mx_fold<ST, DT, V, false, KMAX>(x[r], kf, has_acc, xa[r], e0, a.trunc_from, sc);
         bool hit = WIDE && mx_inf_nan<float>(xa[r]);
 #pragma unroll
         for (int i = 0; i < KMAX; i++)
             if (i < kf) hit |= mx_inf_nan<ST>(x[r][i]);
-        if (__builtin_expect(hit, 0)) res[r] = mx_fold<ST, DT, V, true, KMAX>(x[r], kf, has_acc, xa[r], e0, a.trunc_from);
+        if (__builtin_expect(hit, 0))
+            res[r] = mx_fold<ST, DT, V, true, KMAX>(x[r], kf, has_acc, xa[r], e0, a.trunc_from, sc);
     }
     mx_store<DT, RUNS>(a, a.m, res, first, ne);
+}
+
+template <typename ST, typename DT, unsigned V, int RUNS, int KMAX>
+__global__ __launch_bounds__(kMixedBlock) void mixed_kernel(MXArgs a) {
+    mixed_tile<ST, DT, V, RUNS, KMAX>(a, NoScale());
+}
+
+// The same tile under a multiplier (mi_reduce_bcast_mixed_scaled): a kernel of
+// its own, MXArgs as the unscaled call passes it.
+template <typename ST, typename DT, unsigned V, int RUNS, int KMAX>
+__global__ __launch_bounds__(kMixedBlock) void mixed_scaled_kernel(MXArgs a, ScaleArg sc) {
+    mixed_tile<ST, DT, V, RUNS, KMAX>(a, sc);
 }
 
 // The grid-stride form (launches under mi_set_max_blocks) and the element
@@ -1633,17 +1705,18 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_kernel(MXArgs a) {
 // next input's load in flight while one is combined, every step with the x86
 // NaN bits (bcast_stride_kernel's shape), so a lane still has every load back
 // before its first store.  Same bits as mixed_kernel.
-template <typename ST, typename DT, unsigned V, int RUNS>
-__global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
+template <typename ST, typename DT, unsigned V, int RUNS, typename SC>
+__device__ __forceinline__ void mixed_stride(const MXArgs& a, const SC& sc) {
     using SS = typename Tr<ST>::S;
     constexpr bool WIDE = std::is_same<DT, float>::value;
+    constexpr bool SCALED = !std::is_same<SC, NoScale>::value;
     if (a.scalar_only) {
         for (uint64_t i = (uint64_t)blockIdx.x * kMixedBlock + threadIdx.x; i < a.count;
              i += (uint64_t)gridDim.x * kMixedBlock)
-            mixed_elem<ST, DT, V>(a, i);
+            mixed_elem<ST, DT, V>(a, i, sc);
         return;
     }
-    head_tail(blockIdx.x, a.head, a.tail, a.head + a.ngroups * 8, [&](uint64_t i) { mixed_elem<ST, DT, V>(a, i); });
+    head_tail(blockIdx.x, a.head, a.tail, a.head + a.ngroups * 8, [&](uint64_t i) { mixed_elem<ST, DT, V>(a, i, sc); });
     const int k = a.k;
     const bool has_acc = WIDE && a.acc != nullptr;
     for (uint64_t tile = blockIdx.x; tile * mixed_tile_elems<RUNS>() < a.ngroups * 8; tile += gridDim.x) {
@@ -1656,7 +1729,8 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
 #pragma unroll
             for (int r = 0; r < RUNS; r++) x[r] = mx_load<ST>(rs, mx_off(r, sizeof(SS)));
         };
-        float s[RUNS][4], c[4];
+        // acc's values: the fold's start, or under a multiplier its last operand (mx_fold)
+        float s[RUNS][4], c[4], sa[SCALED ? RUNS : 1][4];
         if constexpr (WIDE) {
             if (has_acc) {
                 const __amdgpu_buffer_rsrc_t rs = tile_rsrc(a.acc, first * 4, ne * 4u);
@@ -1664,10 +1738,14 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
                 for (int r = 0; r < RUNS; r++) {
                     const u32x4 xa = __builtin_amdgcn_raw_buffer_load_b128(rs, mx_off(r, 4), 0, kAuxNT);
 #pragma unroll
-                    for (int e = 0; e < 4; e++) s[r][e] = __uint_as_float(xa[e]);
+                    for (int e = 0; e < 4; e++) {
+                        if constexpr (SCALED) sa[r][e] = __uint_as_float(xa[e]);
+                        else s[r][e] = __uint_as_float(xa[e]);
+                    }
                 }
             }
         }
+        const bool from_acc = SCALED ? false : has_acc;
         load(0, cur);
         for (int i = 0; i < k; i++) {
 #pragma unroll
@@ -1677,8 +1755,17 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
             for (int r = 0; r < RUNS; r++) {
                 mx_widen<ST, true>(cur[r], c);
 #pragma unroll
-                for (int e = 0; e < 4; e++) s[r][e] = (i == 0 && !has_acc) ? c[e] : step<float, OP_SUM, 0u, true>(c[e], s[r][e]);
+                for (int e = 0; e < 4; e++) s[r][e] = (i == 0 && !from_acc) ? c[e] : step<float, OP_SUM, 0u, true>(c[e], s[r][e]);
                 cur[r] = nxt[r];
+            }
+        }
+        if constexpr (SCALED) {
+            const float f = sc.template as<float>();
+#pragma unroll
+            for (int r = 0; r < RUNS; r++) {
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    s[r][e] = has_acc ? mx_scaled_onto<true>(s[r][e], f, sa[r][e]) : mx_scaled<true>(s[r][e], f);
             }
         }
         typename MxRun<DT>::type res[RUNS];
@@ -1698,6 +1785,16 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
         }
         mx_store<DT, RUNS>(a, a.m, res, first, ne);
     }
+}
+
+template <typename ST, typename DT, unsigned V, int RUNS>
+__global__ __launch_bounds__(kMixedBlock) void mixed_stride_kernel(MXArgs a) {
+    mixed_stride<ST, DT, V, RUNS>(a, NoScale());
+}
+
+template <typename ST, typename DT, unsigned V, int RUNS>
+__global__ __launch_bounds__(kMixedBlock) void mixed_scaled_stride_kernel(MXArgs a, ScaleArg sc) {
+    mixed_stride<ST, DT, V, RUNS>(a, sc);
 }
 
 // Byte copy with optional non-temporal stores (ccl_comp_copy), on the
