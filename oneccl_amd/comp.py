@@ -162,9 +162,8 @@ def reduce_multi(inputs: Sequence, out, op: reduction = reduction.sum, flags: Op
                                _stream_handle(stream)), "mi_reduce_multi")
 
 
-def _bcast_args(inputs: Sequence, outs: Sequence, flags: Optional[int], what: str):
-    """The tensor checks reduce_bcast and reduce_bcast_scaled share:
-    (inputs, outs, dtype, count, flags)."""
+def _bcast(what: str, inputs: Sequence, outs: Sequence, op: reduction, flags: Optional[int], stream, *scale) -> None:
+    """reduce_bcast and, with a `scale`, reduce_bcast_scaled: the tensor checks and the call mi_<what>."""
     inputs, outs = list(inputs), list(outs)
     if not inputs or not outs:
         raise ValueError(f"{what} needs at least one input and one output")
@@ -177,7 +176,9 @@ def _bcast_args(inputs: Sequence, outs: Sequence, flags: Optional[int], what: st
         if t.numel() != t0.numel():
             raise ValueError(f"all tensors must have the same numel ({t.numel()} against {t0.numel()})")
     dt, count = _dev_args(inputs + outs, None)
-    return inputs, outs, dt, count, reference_flags(dt) if flags is None else flags
+    args = [void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), void_ptr_array([t.data_ptr() for t in outs]),
+            len(outs), count, int(dt), int(op), reference_flags(dt) if flags is None else flags]
+    check(getattr(mi(), "mi_" + what)(*args, *map(float, scale), _stream_handle(stream)), "mi_" + what)
 
 
 def reduce_bcast(inputs: Sequence, outs: Sequence, op: reduction = reduction.sum, flags: Optional[int] = None,
@@ -185,10 +186,7 @@ def reduce_bcast(inputs: Sequence, outs: Sequence, op: reduction = reduction.sum
     """Every tensor of `outs` = the left fold over `inputs` (as reduce_multi),
     folded once and written to all of them in one pass (mi_reduce_bcast).  An
     output may be one of the inputs; two outputs may not overlap."""
-    inputs, outs, dt, count, f = _bcast_args(inputs, outs, flags, "reduce_bcast")
-    check(mi().mi_reduce_bcast(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs),
-                               void_ptr_array([t.data_ptr() for t in outs]), len(outs), count, int(dt), int(op), f,
-                               _stream_handle(stream)), "mi_reduce_bcast")
+    _bcast("reduce_bcast", inputs, outs, op, flags, stream)
 
 
 def reduce_bcast_scaled(inputs: Sequence, outs: Sequence, scale: float, flags: Optional[int] = None,
@@ -197,16 +195,12 @@ def reduce_bcast_scaled(inputs: Sequence, outs: Sequence, scale: float, flags: O
     multiply applied once to the accumulator before its final rounding
     (mi_reduce_bcast_scaled; scale = 1 / len(inputs) is the mean).  Floating
     tensors only; aliasing as reduce_bcast."""
-    inputs, outs, dt, count, f = _bcast_args(inputs, outs, flags, "reduce_bcast_scaled")
-    check(mi().mi_reduce_bcast_scaled(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs),
-                                      void_ptr_array([t.data_ptr() for t in outs]), len(outs), count, int(dt),
-                                      int(reduction.sum), f, float(scale), _stream_handle(stream)),
-          "mi_reduce_bcast_scaled")
+    _bcast("reduce_bcast_scaled", inputs, outs, reduction.sum, flags, stream, scale)
 
 
-def _mixed_args(inputs: Sequence, outs: Sequence, acc, flags: Optional[int], what: str):
-    """The tensor checks reduce_bcast_mixed and reduce_bcast_mixed_scaled
-    share: (inputs, outs, in dtype, out dtype, count, flags)."""
+def _mixed(what: str, inputs: Sequence, outs: Sequence, acc, flags: Optional[int], stream, *scale) -> None:
+    """reduce_bcast_mixed and, with a `scale`, reduce_bcast_mixed_scaled: the tensor checks and the call
+    mi_<what>."""
     inputs, outs = list(inputs), list(outs)
     if not inputs or not outs:
         raise ValueError(f"{what} needs at least one input and one output")
@@ -235,8 +229,10 @@ def _mixed_args(inputs: Sequence, outs: Sequence, acc, flags: Optional[int], wha
             raise ValueError(f"all tensors must be on one device ({t.device} against {t0.device})")
     if not t0.is_cuda:
         raise ValueError("device entry points take device tensors")
-    f = reference_flags(idt if idt in lp else odt) if flags is None else flags
-    return inputs, outs, idt, odt, t0.numel(), f
+    args = [void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), int(idt),
+            acc.data_ptr() if acc is not None else None, void_ptr_array([t.data_ptr() for t in outs]), len(outs),
+            int(odt), t0.numel(), int(reduction.sum), reference_flags(idt if idt in lp else odt) if flags is None else flags]
+    check(getattr(mi(), "mi_" + what)(*args, *map(float, scale), _stream_handle(stream)), "mi_" + what)
 
 
 def reduce_bcast_mixed(inputs: Sequence, outs: Sequence, acc=None, flags: Optional[int] = None,
@@ -247,11 +243,7 @@ def reduce_bcast_mixed(inputs: Sequence, outs: Sequence, acc=None, flags: Option
     inputs with bf16 or fp16 outputs (no `acc` then); the dtypes are the
     tensors'.  `acc` may be one of the outputs; no output may overlap an input.
     flags=None: reference_flags of the 16-bit dtype."""
-    inputs, outs, idt, odt, count, f = _mixed_args(inputs, outs, acc, flags, "reduce_bcast_mixed")
-    check(mi().mi_reduce_bcast_mixed(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), int(idt),
-                                     acc.data_ptr() if acc is not None else None,
-                                     void_ptr_array([t.data_ptr() for t in outs]), len(outs), int(odt), count,
-                                     int(reduction.sum), f, _stream_handle(stream)), "mi_reduce_bcast_mixed")
+    _mixed("reduce_bcast_mixed", inputs, outs, acc, flags, stream)
 
 
 def reduce_bcast_mixed_scaled(inputs: Sequence, outs: Sequence, scale: float, acc=None,
@@ -262,12 +254,7 @@ def reduce_bcast_mixed_scaled(inputs: Sequence, outs: Sequence, scale: float, ac
     rounding; with `acc`, acc + scale * sum (the product rounded to fp32, then
     one add), which is main_grad += the averaged wire gradients when `acc` is
     one of the outputs.  dtypes, aliasing and flags as reduce_bcast_mixed."""
-    inputs, outs, idt, odt, count, f = _mixed_args(inputs, outs, acc, flags, "reduce_bcast_mixed_scaled")
-    check(mi().mi_reduce_bcast_mixed_scaled(void_ptr_array([t.data_ptr() for t in inputs]), len(inputs), int(idt),
-                                            acc.data_ptr() if acc is not None else None,
-                                            void_ptr_array([t.data_ptr() for t in outs]), len(outs), int(odt), count,
-                                            int(reduction.sum), f, float(scale), _stream_handle(stream)),
-          "mi_reduce_bcast_mixed_scaled")
+    _mixed("reduce_bcast_mixed_scaled", inputs, outs, acc, flags, stream, scale)
 
 
 # ---- the drop-in shim (synchronous, host or device pointers) ------------

@@ -734,240 +734,57 @@ int bcast_planned_waves(int k, int m) {
     return s > 12 ? 6 : fan_waves_per_cu(s);
 }
 
-// Every refusal that needs no device, before any HIP call: the ranges of two
-// outputs may not overlap (equal ones included: which store lands last would
-// be the only difference, but a caller passing one buffer twice has miscounted
-// its ranks), and an output may overlap an input only by being it.
-int check_bcast_args(const void* const* inputs, int k, void* const* outs, int m, size_t count, size_t es) {
-    char msg[160];
-    for (int i = 0; i < k; i++)
-        if (!inputs[i]) {
-            snprintf(msg, sizeof(msg), "inputs[%d] is NULL", i);
-            return fail(MI_E_INVALID, msg);
-        }
-    for (int i = 0; i < m; i++)
-        if (!outs[i]) {
-            snprintf(msg, sizeof(msg), "outs[%d] is NULL", i);
-            return fail(MI_E_INVALID, msg);
-        }
-    if (count == 0) return 0;
-    if (count > UINTPTR_MAX / es) return fail(MI_E_INVALID, "count overflows the address space");
-    const uintptr_t nb = count * es;
-    for (int i = 0; i < k; i++)
-        if (nb > UINTPTR_MAX - reinterpret_cast<uintptr_t>(inputs[i])) {
-            snprintf(msg, sizeof(msg), "inputs[%d] + count overflows the address space", i);
-            return fail(MI_E_INVALID, msg);
-        }
-    for (int i = 0; i < m; i++)
-        if (nb > UINTPTR_MAX - reinterpret_cast<uintptr_t>(outs[i])) {
-            snprintf(msg, sizeof(msg), "outs[%d] + count overflows the address space", i);
-            return fail(MI_E_INVALID, msg);
-        }
-    for (int i = 0; i < m; i++) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(outs[i]), hi = lo + nb;
-        for (int j = 0; j < i; j++) {
-            const uintptr_t l2 = reinterpret_cast<uintptr_t>(outs[j]);
-            if (lo < l2 + nb && l2 < hi) {
-                snprintf(msg, sizeof(msg), "outs[%d] and outs[%d] overlap", j, i);
-                return fail(MI_E_INVALID, msg);
-            }
-        }
-        for (int j = 0; j < k; j++) {
-            const uintptr_t l2 = reinterpret_cast<uintptr_t>(inputs[j]);
-            if (l2 != lo && lo < l2 + nb && l2 < hi) {
-                snprintf(msg, sizeof(msg), "outs[%d] overlaps inputs[%d] without being equal to it", i, j);
-                return fail(MI_E_INVALID, msg);
-            }
-        }
-    }
-    return 0;
+// Whether a fan-out call has a multiplier: SC is the kernels' parameter,
+// NoScale or ScaleArg (reduce_kernels.hpp).
+template <typename SC>
+constexpr bool kScaled = !std::is_same<SC, NoScale>::value;
+
+// The plan every fan-out call launches its tiles under, by its input streams
+// (`acc` one of them) and m: the fan-out's, but for (2, 1).  Two loads and one
+// store per lane is the 2-input reduce's stream, and wants that kernel's plan
+// (21 waves per CU), not the fan-in's for two streams (16).  (The unscaled
+// same-dtype call hands m = 1 to launch_reduce, so it gets here with m >= 2.)
+// mi_reduce_bcast_scaled: at 16 the 1 GiB bf16 sum ran at 0.543 ms against
+// 0.488 for mi_reduce_bcast (which hands m = 1 to the 2-input kernel), at 21 at
+// 0.489; fp32 0.503 / 0.500 / 0.500 (tools/scaled_sweep.py --residency,
+// profiles/reduce_scaled/).  mi_reduce_bcast_mixed: 1 GiB of fp32 from two bf16
+// inputs ran at 0.335 ms at the fan-out's 16 waves and at 0.314 at 21; fp32 to
+// bf16 the same within 1 % at 12, 16 and 21.  At the other shapes measured
+// ((8, 1), (8, 1) with acc, (2, 2), (8, 8)) the plan was the fastest or within
+// 2 % of it (tools/mixed_sweep.py --residency, profiles/reduce_mixed/).  Those
+// figures are the unscaled call's; the scaled mixed call adopts the plan
+// unmeasured (its streams are the same).
+int fanout_waves(int streams_in, int m) {
+    return (streams_in == 2 && m == 1) ? planned_waves(2) : bcast_planned_waves(streams_in, m);
 }
 
-int check_bcast_lists(const void* const* inputs, int k, void* const* outs, int m) {
-    if (k < 1 || k > MI_MAX_INPUTS) return fail(MI_E_INVALID, "input count k out of range [1,16]");
-    if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
-    if (!inputs) return fail(MI_E_INVALID, "null input list");
-    if (!outs) return fail(MI_E_INVALID, "null output list");
-    return 0;
-}
-
-int require_bcast_visible(const void* const* inputs, int k, void* const* outs, int m, size_t bytes) {
-    for (int i = 0; i < k; i++)
-        if (int rc = require_gpu_visible(inputs[i], bytes)) return rc;
-    for (int i = 0; i < m; i++)
-        if (int rc = require_gpu_visible(outs[i], bytes)) return rc;
-    return 0;
-}
-
-// What mi_reduce_bcast and mi_reduce_bcast_scaled share once their arguments
-// have passed and their kernel is picked: the outputs' common 16-byte grid,
-// the residency cap (`waves` per CU), the store policy and the grid-cap
-// routing.  launch(stride_blocks, args, lds) starts the kernel (launch_bcast's
-// convention).
-template <typename Launch>
-int issue_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, size_t es,
-                hipStream_t stream, int waves, Launch&& launch) {
-    // the outputs' common 16-byte grid (vec_grid.hpp)
-    const VecGrid g = plan_vec_grid(es, count, outs, m, inputs, k, unaligned_vectors() != 0);
-
-    BCArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < k; i++) a.in[i] = inputs[i];
-    for (int i = 0; i < m; i++) a.out[i] = outs[i];
-    a.k = k;
-    a.m = m;
-    a.count = count;
-    a.trunc_from = (count / 16) * 16;
-    a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
-    a.head = g.head;
-    a.nvec = g.nvec;
-    a.tail = g.tail;
-    a.scalar_only = !g.vec;
+// Route of a fan-out launch: 0 for one tile per one-wave block (a vector grid,
+// no grid cap, and the tiles fit one launch), else the blocks of the
+// grid-stride form, as stride_grid counts them for the reduce: one per tile of
+// `tile` out of `units` (vectors, or the mixed kernels' elements) up to the
+// cap, or the element loop's blocks of `block` lanes, at most 8192.
+unsigned fanout_stride_blocks(bool vec, bool fits, uint64_t units, uint64_t tile, size_t count, int block) {
     const int cap = max_blocks();
-    hipError_t e;
-    if (g.vec && cap == 0 && g.nvec / kBcastBlock < 0x7FFFFFFFull)
-        e = launch(0u, a, wave_cap_lds(stream, waves));
-    else
-        e = launch(stride_grid(g, kBlock, count, cap), a, 0u);
-    if (e != hipSuccess) return hip_fail(e, "kernel launch");
-    return 0;
+    if (vec && cap == 0 && fits) return 0u;
+    uint64_t blocks;
+    if (vec) {
+        blocks = (units + tile - 1) / tile;
+        if (cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
+    } else {
+        blocks = std::min<uint64_t>((count + block - 1) / block, 8192);
+    }
+    return (unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull);
 }
 
-int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt, int op,
-                        unsigned flags, hipStream_t stream) {
-    size_t es;
-    if (int rc = check_dtype(dt, &es)) return rc;
-    if (int rc = check_op(op)) return rc;
-    if (int rc = check_bcast_lists(inputs, k, outs, m)) return rc;
-    if (int rc = check_bcast_args(inputs, k, outs, m, count, es)) return rc;
-    if (count == 0) return 0;
-    // one output: mi_reduce_multi, its kernels and launch plans
-    if (m == 1) return launch_reduce(inputs, k, outs[0], count, dt, op, flags, stream);
-
-    if (int rc = require_bcast_visible(inputs, k, outs, m, count * es)) return rc;
-    const Kern kern = pick(dt, op, canon_flags(dt, op, flags, k));
-    if (!kern.bcast) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
-    return issue_bcast(inputs, k, outs, m, count, es, stream, bcast_planned_waves(k, m),
-                       [&](unsigned stride_blocks, const BCArgs& a, unsigned lds) {
-                           return kern.bcast(stride_blocks, stream, a, lds);
-                       });
-}
-
-// The multiplier of mi_reduce_bcast_scaled in the compute type: float for
-// fp32, bf16 and fp16 (the conversion rounds to nearest even), double for
-// fp64.  Zero and infinity are refused after the conversion too: inf * 0 would
-// make a NaN whose bits are the multiplier's own choice.
-int check_scale(int dt, double scale, ScaleArg* sc) {
-    if (!std::isfinite(scale)) return fail(MI_E_INVALID, "scale is NaN or infinite");
-    sc->d = scale;
-    sc->f = (float)scale;
-    const bool f64 = dt == MI_FLOAT64;
-    if (f64 ? scale == 0.0 : sc->f == 0.0f)
-        return fail(MI_E_INVALID, f64 ? "scale is zero" : "scale is zero as a float (the compute type)");
-    if (!f64 && std::isinf(sc->f)) return fail(MI_E_INVALID, "scale is infinite as a float (the compute type)");
-    return 0;
-}
-
-int launch_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt,
-                               int op, unsigned flags, double scale, hipStream_t stream) {
-    size_t es;
-    if (int rc = check_dtype(dt, &es)) return rc;
-    if (int rc = check_op(op)) return rc;
-    if (op != MI_OP_SUM) return fail(MI_E_UNSUPPORTED, "op: a scaled reduction is a sum (MI_OP_SUM)");
-    if (dt != MI_FLOAT16 && dt != MI_FLOAT32 && dt != MI_FLOAT64 && dt != MI_BFLOAT16)
-        return fail(MI_E_UNSUPPORTED, "dtype: a scaled reduction needs fp16, bf16, fp32 or fp64");
-    if (int rc = check_bcast_lists(inputs, k, outs, m)) return rc;
-    ScaleArg sc;
-    if (int rc = check_scale(dt, scale, &sc)) return rc;
-    if (int rc = check_bcast_args(inputs, k, outs, m, count, es)) return rc;
-    if (count == 0) return 0;
-    if (int rc = require_bcast_visible(inputs, k, outs, m, count * es)) return rc;
-    // every (k, m), m = 1 and k = 1 included, runs the scaled fan-out kernels
-    const Kern kern = pick(dt, op, canon_flags(dt, op, flags, k));
-    if (!kern.bcast_scaled) return fail(MI_E_UNSUPPORTED, "no scaled kernel for this dtype/variant");
-    // The fan-out's residency plan, but for (2, 1): two loads and one store per
-    // lane is the 2-input reduce's stream, and wants that kernel's plan (21
-    // waves per CU), not the fan-in's for two streams (16).  At 16 the 1 GiB
-    // bf16 sum ran at 0.543 ms against 0.488 for mi_reduce_bcast (which hands
-    // m = 1 to the 2-input kernel), at 21 at 0.489; fp32 0.503 / 0.500 / 0.500
-    // (tools/scaled_sweep.py --residency, profiles/reduce_scaled/).
-    const int waves = (k == 2 && m == 1) ? planned_waves(2) : bcast_planned_waves(k, m);
-    return issue_bcast(inputs, k, outs, m, count, es, stream, waves,
-                       [&](unsigned stride_blocks, const BCArgs& a, unsigned lds) {
-                           return kern.bcast_scaled(stride_blocks, stream, a, sc, lds);
-                       });
-}
-
-// ---------------------------------------------------------------------------
-// fold in fp32 across precisions, write to m outputs (mi_reduce_bcast_mixed)
-// ---------------------------------------------------------------------------
-// Lane layout of the mixed kernels' tiles: a wave's 512 elements as two runs
-// of 4 per lane (convert_kernel's wave chunks).  The alternative, one run of 4
-// per lane, is the same kernel text with RUNS = 1; as compiled it took 238 VGPRs
-// (fp32 in, 8 slots) and 492 with scratch (16-bit in, 16 slots), so it is not
-// built and was not measured (DESIGN.md §6.8).
-constexpr int kMixedRuns = 2;
-
-typedef hipError_t (*LaunchMxFn)(unsigned stride_blocks, unsigned tiles, hipStream_t, const MXArgs&, unsigned lds);
-
-// stride_blocks = 0: one tile per one-wave block (8 input slots for k <= 8,
-// else 16), capped by `lds` like the fan-out.  Otherwise the grid-stride form
-// with that many blocks (a grid cap, or the element loop).
-template <typename ST, typename DT, unsigned V, int RUNS>
-hipError_t launch_mixed(unsigned stride_blocks, unsigned tiles, hipStream_t s, const MXArgs& a, unsigned lds) {
-    if (stride_blocks)
-        hipLaunchKernelGGL((mixed_stride_kernel<ST, DT, V, RUNS>), dim3(stride_blocks), dim3(kMixedBlock), 0, s, a);
-    else if (a.k <= 8)
-        hipLaunchKernelGGL((mixed_kernel<ST, DT, V, RUNS, 8>), dim3(tiles), dim3(kMixedBlock), lds, s, a);
-    else
-        hipLaunchKernelGGL((mixed_kernel<ST, DT, V, RUNS, kMaxInputs>), dim3(tiles), dim3(kMixedBlock), lds, s, a);
-    return hipGetLastError();
-}
-
-// mi_reduce_bcast_mixed_scaled: launch_mixed's routing onto the kernels with a multiplier.
-typedef hipError_t (*LaunchMxScFn)(unsigned stride_blocks, unsigned tiles, hipStream_t, const MXArgs&, const ScaleArg&,
-                                   unsigned lds);
-
-template <typename ST, typename DT, unsigned V, int RUNS>
-hipError_t launch_mixed_scaled(unsigned stride_blocks, unsigned tiles, hipStream_t s, const MXArgs& a,
-                               const ScaleArg& sc, unsigned lds) {
-    if (stride_blocks)
-        hipLaunchKernelGGL((mixed_scaled_stride_kernel<ST, DT, V, RUNS>), dim3(stride_blocks), dim3(kMixedBlock), 0, s, a,
-                           sc);
-    else if (a.k <= 8)
-        hipLaunchKernelGGL((mixed_scaled_kernel<ST, DT, V, RUNS, 8>), dim3(tiles), dim3(kMixedBlock), lds, s, a, sc);
-    else
-        hipLaunchKernelGGL((mixed_scaled_kernel<ST, DT, V, RUNS, kMaxInputs>), dim3(tiles), dim3(kMixedBlock), lds, s, a,
-                           sc);
-    return hipGetLastError();
-}
-
-LaunchMxScFn pick_mixed_scaled(int idt, int odt, unsigned v) {
-    constexpr int RUNS = kMixedRuns;
-    if (idt == MI_BFLOAT16) return &launch_mixed_scaled<bf16_tag, float, 0u, RUNS>;
-    if (idt == MI_FLOAT16) return &launch_mixed_scaled<fp16_tag, float, 0u, RUNS>;
-    if (odt == MI_FLOAT16) return &launch_mixed_scaled<float, fp16_tag, 0u, RUNS>;
-    if (!(v & V_BF16_RNE)) return &launch_mixed_scaled<float, bf16_tag, 0u, RUNS>;
-    return (v & V_TAIL_TRUNC) ? &launch_mixed_scaled<float, bf16_tag, V_BF16_RNE | V_TAIL_TRUNC, RUNS>
-                              : &launch_mixed_scaled<float, bf16_tag, V_BF16_RNE, RUNS>;
-}
-
-LaunchMxFn pick_mixed(int idt, int odt, unsigned v) {
-    constexpr int RUNS = kMixedRuns;
-    if (idt == MI_BFLOAT16) return &launch_mixed<bf16_tag, float, 0u, RUNS>;
-    if (idt == MI_FLOAT16) return &launch_mixed<fp16_tag, float, 0u, RUNS>;
-    if (odt == MI_FLOAT16) return &launch_mixed<float, fp16_tag, 0u, RUNS>;
-    if (!(v & V_BF16_RNE)) return &launch_mixed<float, bf16_tag, 0u, RUNS>;
-    return (v & V_TAIL_TRUNC) ? &launch_mixed<float, bf16_tag, V_BF16_RNE | V_TAIL_TRUNC, RUNS>
-                              : &launch_mixed<float, bf16_tag, V_BF16_RNE, RUNS>;
-}
-
-// Every refusal, before any HIP call.  Ranges are computed with each side's
-// own element size; an output may overlap no input at all (the element sizes
-// differ, so no lane would load exactly the bytes it stores), and `acc` only
-// by being it.
-int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void* acc, void* const* outs, int m,
-                     size_t es_out, size_t count) {
+// Every refusal of a fan-out call that needs no device, before any HIP call.
+// Ranges are computed with each side's own element size (`acc` is fp32).  The
+// ranges of two outputs may not overlap (equal ones included: which store lands
+// last would be the only difference, but a caller passing one buffer twice has
+// miscounted its ranks).  An output may overlap an input only by being it, and
+// across element sizes not at all (no lane would load exactly the bytes it
+// stores); `acc` only by being it.
+int check_fanout_args(const void* const* inputs, int k, size_t es_in, const void* acc, void* const* outs, int m,
+                      size_t es_out, size_t count) {
     char msg[160];
     for (int i = 0; i < k; i++)
         if (!inputs[i]) {
@@ -980,7 +797,7 @@ int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void*
             return fail(MI_E_INVALID, msg);
         }
     if (count == 0) return 0;
-    if (count > UINTPTR_MAX / 4) return fail(MI_E_INVALID, "count overflows the address space");
+    if (count > UINTPTR_MAX / std::max(es_in, es_out)) return fail(MI_E_INVALID, "count overflows the address space");
     const uintptr_t nbi = count * es_in, nbo = count * es_out, nba = count * 4;
     for (int i = 0; i < k; i++)
         if (nbi > UINTPTR_MAX - reinterpret_cast<uintptr_t>(inputs[i])) {
@@ -994,6 +811,7 @@ int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void*
             snprintf(msg, sizeof(msg), "outs[%d] + count overflows the address space", i);
             return fail(MI_E_INVALID, msg);
         }
+    const bool in_place = es_in == es_out;  // an output may be an input
     for (int i = 0; i < m; i++) {
         const uintptr_t lo = reinterpret_cast<uintptr_t>(outs[i]), hi = lo + nbo;
         for (int j = 0; j < i; j++) {
@@ -1005,8 +823,11 @@ int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void*
         }
         for (int j = 0; j < k; j++) {
             const uintptr_t l2 = reinterpret_cast<uintptr_t>(inputs[j]);
-            if (lo < l2 + nbi && l2 < hi) {
-                snprintf(msg, sizeof(msg), "outs[%d] overlaps inputs[%d] (no in-place form across element sizes)", i, j);
+            if (!(in_place && l2 == lo) && lo < l2 + nbi && l2 < hi) {
+                snprintf(msg, sizeof(msg),
+                         in_place ? "outs[%d] overlaps inputs[%d] without being equal to it"
+                                  : "outs[%d] overlaps inputs[%d] (no in-place form across element sizes)",
+                         i, j);
                 return fail(MI_E_INVALID, msg);
             }
         }
@@ -1018,9 +839,171 @@ int check_mixed_args(const void* const* inputs, int k, size_t es_in, const void*
     return 0;
 }
 
-// The checks mi_reduce_bcast_mixed and mi_reduce_bcast_mixed_scaled make before
-// they look at an operand, in the documented order: the dtype pair, the op,
-// acc against the direction, k and m, the lists.
+// k (`acc` counts against MI_MAX_INPUTS), m and the two lists
+int check_fanout_lists(const void* const* inputs, int k, const void* acc, void* const* outs, int m) {
+    if (k < 1 || k > MI_MAX_INPUTS - (acc ? 1 : 0))
+        return fail(MI_E_INVALID, acc ? "input count k out of range [1,15] (acc counts against MI_MAX_INPUTS)"
+                                      : "input count k out of range [1,16]");
+    if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
+    if (!inputs) return fail(MI_E_INVALID, "null input list");
+    if (!outs) return fail(MI_E_INVALID, "null output list");
+    return 0;
+}
+
+// The multiplier of the scaled calls in the compute type: float for fp32, bf16
+// and fp16 (the conversion rounds to nearest even), double for fp64.  Zero and
+// infinity are refused after the conversion too: inf * 0 would make a NaN
+// whose bits are the multiplier's own choice.  An unscaled call has none.
+int check_scale(int, double, NoScale*) { return 0; }
+int check_scale(int dt, double scale, ScaleArg* sc) {
+    if (!std::isfinite(scale)) return fail(MI_E_INVALID, "scale is NaN or infinite");
+    sc->d = scale;
+    sc->f = (float)scale;
+    const bool f64 = dt == MI_FLOAT64;
+    if (f64 ? scale == 0.0 : sc->f == 0.0f)
+        return fail(MI_E_INVALID, f64 ? "scale is zero" : "scale is zero as a float (the compute type)");
+    if (!f64 && std::isinf(sc->f)) return fail(MI_E_INVALID, "scale is infinite as a float (the compute type)");
+    return 0;
+}
+
+// Every operand of a fan-out call must be device memory or device-visible.
+int require_fanout_visible(const void* const* inputs, int k, size_t bytes_in, const void* acc, size_t bytes_acc,
+                           void* const* outs, int m, size_t bytes_out) {
+    for (int i = 0; i < k; i++)
+        if (int rc = require_gpu_visible(inputs[i], bytes_in)) return rc;
+    if (acc)
+        if (int rc = require_gpu_visible(acc, bytes_acc)) return rc;
+    for (int i = 0; i < m; i++)
+        if (int rc = require_gpu_visible(outs[i], bytes_out)) return rc;
+    return 0;
+}
+
+// The kernel arguments BCArgs and MXArgs have in common, from the operands and
+// the outputs' grid (a VecGrid or a MixedGrid).
+template <typename Args, typename Grid>
+Args fanout_kargs(const void* const* inputs, int k, void* const* outs, int m, size_t count, const Grid& g) {
+    Args a;
+    memset(&a, 0, sizeof(a));
+    for (int i = 0; i < k; i++) a.in[i] = inputs[i];
+    for (int i = 0; i < m; i++) a.out[i] = outs[i];
+    a.k = k;
+    a.m = m;
+    a.count = count;
+    a.trunc_from = (count / 16) * 16;
+    a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
+    a.head = g.head;
+    a.tail = g.tail;
+    a.scalar_only = !g.vec;
+    return a;
+}
+
+// What is left of mi_reduce_bcast and mi_reduce_bcast_scaled once their
+// arguments have passed and their kernel is picked: the outputs' common
+// 16-byte grid, the residency cap, the store policy and the route.
+template <typename SC>
+int issue_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, size_t es,
+                hipStream_t stream, const Kern& kern, const SC& sc) {
+    // the outputs' common 16-byte grid (vec_grid.hpp)
+    const VecGrid g = plan_vec_grid(es, count, outs, m, inputs, k, unaligned_vectors() != 0);
+
+    BCArgs a = fanout_kargs<BCArgs>(inputs, k, outs, m, count, g);
+    a.nvec = g.nvec;
+    const unsigned stride_blocks =
+        fanout_stride_blocks(g.vec, g.nvec / kBcastBlock < 0x7FFFFFFFull, g.nvec, kBlock, count, kBlock);
+    const unsigned lds = stride_blocks ? 0u : wave_cap_lds(stream, fanout_waves(k, m));
+    hipError_t e;
+    if constexpr (kScaled<SC>) e = kern.bcast_scaled(stride_blocks, stream, a, sc, lds);
+    else e = kern.bcast(stride_blocks, stream, a, lds);
+    if (e != hipSuccess) return hip_fail(e, "kernel launch");
+    return 0;
+}
+
+// mi_reduce_bcast (SC = NoScale; `scale` unused) and mi_reduce_bcast_scaled
+// (ScaleArg): a sum of a floating type, its multiplier checked after the lists
+// and before the operands, and kernels of its own for every (k, m).
+template <typename SC>
+int launch_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dt, int op,
+                        unsigned flags, double scale, hipStream_t stream) {
+    size_t es;
+    if (int rc = check_dtype(dt, &es)) return rc;
+    if (int rc = check_op(op)) return rc;
+    if constexpr (kScaled<SC>) {
+        if (op != MI_OP_SUM) return fail(MI_E_UNSUPPORTED, "op: a scaled reduction is a sum (MI_OP_SUM)");
+        if (dt != MI_FLOAT16 && dt != MI_FLOAT32 && dt != MI_FLOAT64 && dt != MI_BFLOAT16)
+            return fail(MI_E_UNSUPPORTED, "dtype: a scaled reduction needs fp16, bf16, fp32 or fp64");
+    }
+    if (int rc = check_fanout_lists(inputs, k, nullptr, outs, m)) return rc;
+    SC sc;
+    if (int rc = check_scale(dt, scale, &sc)) return rc;
+    if (int rc = check_fanout_args(inputs, k, es, nullptr, outs, m, es, count)) return rc;
+    if (count == 0) return 0;
+    // one output, unscaled: mi_reduce_multi, its kernels and launch plans
+    if (!kScaled<SC> && m == 1) return launch_reduce(inputs, k, outs[0], count, dt, op, flags, stream);
+
+    if (int rc = require_fanout_visible(inputs, k, count * es, nullptr, 0, outs, m, count * es)) return rc;
+    const Kern kern = pick(dt, op, canon_flags(dt, op, flags, k));
+    if (kScaled<SC> ? !kern.bcast_scaled : !kern.bcast)
+        return fail(MI_E_UNSUPPORTED,
+                    kScaled<SC> ? "no scaled kernel for this dtype/variant" : "no kernel for this dtype/op/variant");
+    return issue_bcast(inputs, k, outs, m, count, es, stream, kern, sc);
+}
+
+// ---------------------------------------------------------------------------
+// fold in fp32 across precisions, write to m outputs (mi_reduce_bcast_mixed)
+// ---------------------------------------------------------------------------
+// Lane layout of the mixed kernels' tiles: a wave's 512 elements as two runs
+// of 4 per lane (convert_kernel's wave chunks).  The alternative, one run of 4
+// per lane, is the same kernel text with RUNS = 1; as compiled it took 238 VGPRs
+// (fp32 in, 8 slots) and 492 with scratch (16-bit in, 16 slots), so it is not
+// built and was not measured (DESIGN.md §6.8).
+constexpr int kMixedRuns = 2;
+
+// A mixed launcher, without (SC = NoScale) or with a multiplier (ScaleArg)
+template <typename SC>
+using LaunchMxFn = hipError_t (*)(unsigned stride_blocks, unsigned tiles, hipStream_t, const MXArgs&, const SC&,
+                                  unsigned lds);
+
+// mi_reduce_bcast_mixed and, under a multiplier (SC = ScaleArg),
+// mi_reduce_bcast_mixed_scaled.  stride_blocks = 0: one tile per one-wave
+// block (8 input slots for k <= 8, else 16), capped by `lds` like the fan-out.
+// Otherwise the grid-stride form with that many blocks (a grid cap, or the
+// element loop).
+template <typename ST, typename DT, unsigned V, int RUNS, typename SC>
+hipError_t launch_mixed(unsigned stride_blocks, unsigned tiles, hipStream_t s, const MXArgs& a, const SC& sc,
+                        unsigned lds) {
+    const dim3 grid(stride_blocks ? stride_blocks : tiles), block(kMixedBlock);
+    if constexpr (kScaled<SC>) {  // only this branch names a kernel with a multiplier
+        if (stride_blocks)
+            hipLaunchKernelGGL((mixed_scaled_stride_kernel<ST, DT, V, RUNS>), grid, block, 0, s, a, sc);
+        else if (a.k <= 8)
+            hipLaunchKernelGGL((mixed_scaled_kernel<ST, DT, V, RUNS, 8>), grid, block, lds, s, a, sc);
+        else
+            hipLaunchKernelGGL((mixed_scaled_kernel<ST, DT, V, RUNS, kMaxInputs>), grid, block, lds, s, a, sc);
+    } else {
+        if (stride_blocks)
+            hipLaunchKernelGGL((mixed_stride_kernel<ST, DT, V, RUNS>), grid, block, 0, s, a);
+        else if (a.k <= 8)
+            hipLaunchKernelGGL((mixed_kernel<ST, DT, V, RUNS, 8>), grid, block, lds, s, a);
+        else
+            hipLaunchKernelGGL((mixed_kernel<ST, DT, V, RUNS, kMaxInputs>), grid, block, lds, s, a);
+    }
+    return hipGetLastError();
+}
+
+template <typename SC>
+LaunchMxFn<SC> pick_mixed(int idt, int odt, unsigned v) {
+    constexpr int RUNS = kMixedRuns;
+    if (idt == MI_BFLOAT16) return &launch_mixed<bf16_tag, float, 0u, RUNS, SC>;
+    if (idt == MI_FLOAT16) return &launch_mixed<fp16_tag, float, 0u, RUNS, SC>;
+    if (odt == MI_FLOAT16) return &launch_mixed<float, fp16_tag, 0u, RUNS, SC>;
+    if (!(v & V_BF16_RNE)) return &launch_mixed<float, bf16_tag, 0u, RUNS, SC>;
+    return (v & V_TAIL_TRUNC) ? &launch_mixed<float, bf16_tag, V_BF16_RNE | V_TAIL_TRUNC, RUNS, SC>
+                              : &launch_mixed<float, bf16_tag, V_BF16_RNE, RUNS, SC>;
+}
+
+// The checks the mixed calls make before they look at an operand, in the
+// documented order: the dtype pair, the op, acc against the direction, then
+// check_fanout_lists.
 int check_mixed_lists(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m, int odt,
                       int op, bool* narrowing_out) {
     const bool widening = (idt == MI_BFLOAT16 || idt == MI_FLOAT16) && odt == MI_FLOAT32;
@@ -1031,105 +1014,51 @@ int check_mixed_lists(const void* const* inputs, int k, int idt, const void* acc
                     "(equal dtypes: mi_reduce_bcast)");
     if (op != MI_OP_SUM) return fail(MI_E_UNSUPPORTED, "op: a mixed-precision reduction is a sum (MI_OP_SUM)");
     if (acc && narrowing) return fail(MI_E_UNSUPPORTED, "acc: an accumulator is fp32, so only a widening call takes one");
-    const int kmax = MI_MAX_INPUTS - (acc ? 1 : 0);
-    if (k < 1 || k > kmax)
-        return fail(MI_E_INVALID, acc ? "input count k out of range [1,15] (acc counts against MI_MAX_INPUTS)"
-                                      : "input count k out of range [1,16]");
-    if (m < 1 || m > MI_MAX_INPUTS) return fail(MI_E_INVALID, "output count m out of range [1,16]");
-    if (!inputs) return fail(MI_E_INVALID, "null input list");
-    if (!outs) return fail(MI_E_INVALID, "null output list");
     *narrowing_out = narrowing;
-    return 0;
+    return check_fanout_lists(inputs, k, acc, outs, m);
 }
 
-// What the two calls share once their arguments have passed: the visibility
-// checks, the variant, the outputs' grid, the residency plan and the grid-cap
-// routing.  launch(v, stride_blocks, tiles, args, lds) starts the kernel of
-// variant bits v (launch_mixed's convention).
-template <typename Launch>
+// What is left of the two mixed calls once their arguments have passed: the
+// visibility checks, the variant, the outputs' grid, the residency cap, the
+// store policy and the route.
+template <typename SC>
 int issue_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m, int odt,
-                size_t count, int op, unsigned flags, bool narrowing, hipStream_t stream, Launch&& launch) {
+                size_t count, int op, unsigned flags, bool narrowing, hipStream_t stream, const SC& sc) {
     const size_t es_in = dtype_size(idt), es_out = dtype_size(odt);
-    for (int i = 0; i < k; i++)
-        if (int rc = require_gpu_visible(inputs[i], count * es_in)) return rc;
-    if (acc)
-        if (int rc = require_gpu_visible(acc, count * 4)) return rc;
-    for (int i = 0; i < m; i++)
-        if (int rc = require_gpu_visible(outs[i], count * es_out)) return rc;
+    if (int rc = require_fanout_visible(inputs, k, count * es_in, acc, count * 4, outs, m, count * es_out)) return rc;
 
     // the variant bits that change a bit: the narrowing conversion's (canon_flags)
     const unsigned v = narrowing ? (canon_flags(odt, op, flags | V_ACC_FP32, k) & (V_BF16_RNE | V_TAIL_TRUNC)) : 0u;
 
     const MixedGrid g = plan_mixed_grid(es_in, es_out, count, outs, m, inputs, k, acc, unaligned_vectors() != 0);
-    MXArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < k; i++) a.in[i] = inputs[i];
-    for (int i = 0; i < m; i++) a.out[i] = outs[i];
+    MXArgs a = fanout_kargs<MXArgs>(inputs, k, outs, m, count, g);
     a.acc = acc;
-    a.k = k;
-    a.m = m;
-    a.count = count;
-    a.trunc_from = (count / 16) * 16;
-    a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
-    a.head = g.head;
     a.ngroups = g.ngroups;
-    a.tail = g.tail;
-    a.scalar_only = !g.vec;
     const uint64_t te = mixed_tile_elems<kMixedRuns>();
     const uint64_t tiles = std::max<uint64_t>((g.ngroups * 8 + te - 1) / te, 1);
-    const int cap = max_blocks();
-    hipError_t e;
-    if (g.vec && cap == 0 && tiles <= 0x7FFFFFFFull) {
-        // The fan-out's residency plan by streams, acc one of them, but for two
-        // loads and one store per lane, which is the 2-input reduce's stream and
-        // wants that kernel's plan (21 waves per CU, as mi_reduce_bcast_scaled's
-        // (2, 1)): 1 GiB of fp32 from two bf16 inputs ran at 0.335 ms at the
-        // fan-out's 16 waves and at 0.314 at 21; fp32 to bf16 the same within 1 %
-        // at 12, 16 and 21.  At the other shapes measured ((8, 1), (8, 1) with
-        // acc, (2, 2), (8, 8)) the plan was the fastest or within 2 % of it
-        // (tools/mixed_sweep.py --residency, profiles/reduce_mixed/).  Those
-        // figures are the unscaled call's; the scaled call adopts the plan
-        // unmeasured (its streams are the same).
-        const int ks = k + (acc ? 1 : 0);
-        const int waves = (ks == 2 && m == 1) ? planned_waves(2) : bcast_planned_waves(ks, m);
-        e = launch(v, 0u, (unsigned)tiles, a, wave_cap_lds(stream, waves));
-    } else {
-        uint64_t blocks = g.vec ? tiles : std::min<uint64_t>((count + kMixedBlock - 1) / kMixedBlock, 8192);
-        if (g.vec && cap > 0) blocks = std::min<uint64_t>(blocks, (uint64_t)cap);
-        e = launch(v, (unsigned)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 0x7FFFFFFFull), 0u, a, 0u);
-    }
+    const unsigned stride_blocks =
+        fanout_stride_blocks(g.vec, tiles <= 0x7FFFFFFFull, g.ngroups * 8, te, count, kMixedBlock);
+    const unsigned lds = stride_blocks ? 0u : wave_cap_lds(stream, fanout_waves(k + (acc ? 1 : 0), m));
+    const hipError_t e =
+        pick_mixed<SC>(idt, odt, v)(stride_blocks, stride_blocks ? 0u : (unsigned)tiles, stream, a, sc, lds);
     if (e != hipSuccess) return hip_fail(e, "kernel launch");
     return 0;
 }
 
-int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m,
-                              int odt, size_t count, int op, unsigned flags, hipStream_t stream) {
-    bool narrowing;
-    if (int rc = check_mixed_lists(inputs, k, idt, acc, outs, m, odt, op, &narrowing)) return rc;
-    if (int rc = check_mixed_args(inputs, k, dtype_size(idt), acc, outs, m, dtype_size(odt), count)) return rc;
-    if (count == 0) return 0;
-    return issue_mixed(inputs, k, idt, acc, outs, m, odt, count, op, flags, narrowing, stream,
-                       [&](unsigned v, unsigned stride_blocks, unsigned tiles, const MXArgs& a, unsigned lds) {
-                           return pick_mixed(idt, odt, v)(stride_blocks, tiles, stream, a, lds);
-                       });
-}
-
-// mi_reduce_bcast_mixed_scaled: the same call with the multiplier of
+// mi_reduce_bcast_mixed (SC = NoScale; `scale` unused) and
+// mi_reduce_bcast_mixed_scaled (ScaleArg): the multiplier of
 // mi_reduce_bcast_scaled in the float compute type (check_scale with an fp32
 // dtype), refused after the list checks and before the operands', as there.
-int launch_reduce_bcast_mixed_scaled(const void* const* inputs, int k, int idt, const void* acc, void* const* outs,
-                                     int m, int odt, size_t count, int op, unsigned flags, double scale,
-                                     hipStream_t stream) {
+template <typename SC>
+int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m,
+                              int odt, size_t count, int op, unsigned flags, double scale, hipStream_t stream) {
     bool narrowing;
     if (int rc = check_mixed_lists(inputs, k, idt, acc, outs, m, odt, op, &narrowing)) return rc;
-    ScaleArg sc;
+    SC sc;
     if (int rc = check_scale(MI_FLOAT32, scale, &sc)) return rc;
-    if (int rc = check_mixed_args(inputs, k, dtype_size(idt), acc, outs, m, dtype_size(odt), count)) return rc;
+    if (int rc = check_fanout_args(inputs, k, dtype_size(idt), acc, outs, m, dtype_size(odt), count)) return rc;
     if (count == 0) return 0;
-    return issue_mixed(inputs, k, idt, acc, outs, m, odt, count, op, flags, narrowing, stream,
-                       [&](unsigned v, unsigned stride_blocks, unsigned tiles, const MXArgs& a, unsigned lds) {
-                           return pick_mixed_scaled(idt, odt, v)(stride_blocks, tiles, stream, a, sc, lds);
-                       });
+    return issue_mixed(inputs, k, idt, acc, outs, m, odt, count, op, flags, narrowing, stream, sc);
 }
 
 // ---------------------------------------------------------------------------
@@ -2405,25 +2334,25 @@ int mi_reduce_multi(const void* const* inputs, int k, void* out, size_t count, i
 
 int mi_reduce_bcast(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dtype, int op,
                     unsigned flags, void* stream) {
-    return launch_reduce_bcast(inputs, k, outs, m, count, dtype, op, flags, (hipStream_t)stream);
+    return launch_reduce_bcast<NoScale>(inputs, k, outs, m, count, dtype, op, flags, 0.0, (hipStream_t)stream);
 }
 
 int mi_reduce_bcast_scaled(const void* const* inputs, int k, void* const* outs, int m, size_t count, int dtype,
                            int op, unsigned flags, double scale, void* stream) {
-    return launch_reduce_bcast_scaled(inputs, k, outs, m, count, dtype, op, flags, scale, (hipStream_t)stream);
+    return launch_reduce_bcast<ScaleArg>(inputs, k, outs, m, count, dtype, op, flags, scale, (hipStream_t)stream);
 }
 
 int mi_reduce_bcast_mixed(const void* const* inputs, int k, int in_dtype, const void* acc, void* const* outs, int m,
                           int out_dtype, size_t count, int op, unsigned flags, void* stream) {
-    return launch_reduce_bcast_mixed(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags,
-                                     (hipStream_t)stream);
+    return launch_reduce_bcast_mixed<NoScale>(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags, 0.0,
+                                              (hipStream_t)stream);
 }
 
 int mi_reduce_bcast_mixed_scaled(const void* const* inputs, int k, int in_dtype, const void* acc, void* const* outs,
                                  int m, int out_dtype, size_t count, int op, unsigned flags, double scale,
                                  void* stream) {
-    return launch_reduce_bcast_mixed_scaled(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags, scale,
-                                            (hipStream_t)stream);
+    return launch_reduce_bcast_mixed<ScaleArg>(inputs, k, in_dtype, acc, outs, m, out_dtype, count, op, flags, scale,
+                                               (hipStream_t)stream);
 }
 
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op, unsigned flags,

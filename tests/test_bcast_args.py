@@ -116,6 +116,13 @@ def test_bad_dtype_and_custom_op():
 def test_count_overflowing_the_address_space():
     rc, msg = _call([1 << 20, 2 << 20], [3 << 20, 4 << 20], count=(1 << 63))
     assert rc == E_INVALID and "overflows" in msg
+    # the limit is the dtype's: 2^61 elements wrap at 8 bytes each (int64), one fewer end past the top
+    rc, msg = _call([1 << 20, 2 << 20], [3 << 20, 4 << 20], count=1 << 61, dt=6)
+    assert rc == E_INVALID and msg == "count overflows the address space"
+    rc, msg = _call([1 << 20, 2 << 20], [3 << 20, 4 << 20], count=(1 << 61) - 1, dt=6)
+    assert rc == E_INVALID and msg == "inputs[0] + count overflows the address space"
+    rc, msg = _call([1 << 20, 2 << 20], [3 << 20, 4 << 20], count=1 << 61)  # fp32: 2^63 bytes fit
+    assert rc == E_INVALID and msg == "outs[0] overlaps inputs[0] without being equal to it"
 
 
 def test_empty_call_with_valid_arguments_returns_zero():

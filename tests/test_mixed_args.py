@@ -108,6 +108,12 @@ def test_null_lists_and_entries(idt, odt):
 def test_address_overflow():
     rc, msg = _call(_addrs(2), _addrs(2, 0x30000000), count=1 << 63)
     assert rc == E_INVALID and "overflows" in msg
+    # the limit is the wider side's, whichever side that is: 2^62 elements wrap as fp32 only
+    for idt, odt in ((BF16, FP32), (FP32, BF16)):
+        rc, msg = _call(_addrs(1), _addrs(1, 0x30000000), idt=idt, odt=odt, count=1 << 62)
+        assert rc == E_INVALID and msg == "count overflows the address space"
+        rc, msg = _call(_addrs(1), _addrs(1, 0x30000000), idt=idt, odt=odt, count=(1 << 62) - 1)
+        assert rc == E_INVALID and msg == ("outs" if odt == FP32 else "inputs") + "[0] + count overflows the address space"
     top = (1 << 64) - 0x1000
     rc, msg = _call([0x10000000, top], _addrs(1, 0x30000000), count=0x1000)  # 2-byte inputs: 0x2000 bytes
     assert rc == E_INVALID and "inputs[1] + count overflows" in msg

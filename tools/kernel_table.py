@@ -4,6 +4,7 @@ object's metadata (as tests/test_kernel_resources.py reads it; no GPU):
 
   python tools/kernel_table.py LIB > table.tsv
   python tools/kernel_table.py LIB_A LIB_B      # both tables side by side, differing rows marked
+  python tools/kernel_table.py LIB_A LIB_B --text   # kernels whose instruction text differs, or in one library only
 
 Columns: vgpr, sgpr, scratch bytes, vgpr spills, sgpr spills, demangled name."""
 from __future__ import annotations
@@ -43,7 +44,32 @@ def table(lib: Path) -> dict[str, tuple[int, ...]]:
     return {re.sub(r"^void ", "", d): rows[n] for n, d in zip(names, dem)}
 
 
+def text(lib: Path) -> dict[str, str]:
+    """Instruction text per symbol of the code object: the disassembly without
+    addresses, encodings and the trailing `//` comments."""
+    with tempfile.TemporaryDirectory() as tmp:
+        dis = subprocess.run([str(LLVM / "llvm-objdump"), "-d", str(_code_object(lib, Path(tmp)))], check=True,
+                             capture_output=True, text=True).stdout
+    out, fn = {}, None
+    for line in dis.splitlines():
+        if m := re.match(r"^[0-9a-f]+ <(\S+)>:$", line):
+            fn = m.group(1)
+            out[fn] = ""
+        elif fn and line.strip():
+            out[fn] += line.split("//")[0].strip() + "\n"
+    return out
+
+
 def main():
+    if sys.argv[3:] == ["--text"]:
+        a, b = text(Path(sys.argv[1])), text(Path(sys.argv[2]))
+        for name in sorted(a.keys() | b.keys()):
+            if a.get(name) != b.get(name):
+                print(("differs" if name in a and name in b else "only in A" if name in a else "only in B") + "\t" + name)
+        print(f"# kernels: {len(a)} -> {len(b)}; only in A: {len(a.keys() - b.keys())}; only in B: "
+              f"{len(b.keys() - a.keys())}; instruction text differs: "
+              f"{sum(1 for n in a.keys() & b.keys() if a[n] != b[n])}")
+        return
     if len(sys.argv) == 2:
         print("vgpr\tsgpr\tscratch\tvspill\tsspill\tkernel")
         for name, r in sorted(table(Path(sys.argv[1])).items()):
