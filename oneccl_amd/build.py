@@ -67,7 +67,7 @@ HOST_REDUCE_AVX512_FLAGS = HOST_REDUCE_FLAGS + ["-mavx512f", "-mavx512bw", "-mav
 def build_shim(force: bool = False) -> Path:
     out = LIB / "libccl_comp_hip.so"
     deps = [CSRC / "comp.cpp", CSRC / "host_reduce.cpp", CSRC / "host_reduce_avx512.cpp", CSRC / "host_lp.hpp",
-            CSRC / "ccl_mirror.hpp", ROOT / "include" / "mi_reduce.h",
+            CSRC / "variant.hpp", CSRC / "ccl_mirror.hpp", ROOT / "include" / "mi_reduce.h",
             ROOT / "include" / "mi_ccl_comp.h", ROOT / "include" / "mi_ccl_comp_async.hpp",
             ROOT / "include" / "mi_host_reduce.h", LIB / "libmi_reduce.so"]
     if force or _stale(out, deps):
@@ -228,7 +228,7 @@ def build_asan(force: bool = False) -> Path:
         _run([_hipcc(), f"--offload-arch={ARCH}", "-O1", "-g", "-std=c++17", "-fPIC", "-shared", *san,
               "-o", str(mi), str(CSRC / "mi_reduce.hip")])
     shim = adir / "libccl_comp_hip.so"
-    if force or _stale(shim, [CSRC / "comp.cpp", CSRC / "ccl_mirror.hpp", ROOT / "include" / "mi_ccl_comp_async.hpp", mi]):
+    if force or _stale(shim, [CSRC / "comp.cpp", CSRC / "variant.hpp", CSRC / "ccl_mirror.hpp", ROOT / "include" / "mi_ccl_comp_async.hpp", mi]):
         # the same compiler (and so the same ASan runtime) as the hipcc-built pieces
         clang = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", "/opt/rocm/llvm/bin/clang++")
                       if Path(c).exists()), "clang++")

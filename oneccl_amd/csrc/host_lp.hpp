@@ -18,7 +18,7 @@
 #include <cstdint>
 #include <cstring>
 
-#include "../../include/mi_reduce.h"
+#include "variant.hpp"  // include/mi_reduce.h and tail_trunc_from
 
 namespace mi_host {
 
@@ -92,7 +92,7 @@ void lp_fold(const void* const* inputs, int k, void* out, size_t count, unsigned
     uint16_t* dst = static_cast<uint16_t*>(out);
     // keep-precision's final conversion truncates the count % 16 tail: a
     // multiple of 16, so whole groups (8 or 16 lanes) fall on either side
-    const size_t rne_end = (RNE && ACC32 && (v & MI_F_BF16_TAIL_TRUNC16)) ? (count / 16) * 16 : count;
+    const size_t rne_end = (RNE && ACC32 && (v & MI_F_BF16_TAIL_TRUNC16)) ? mi::tail_trunc_from(count) : count;
     lp_range<V, BF, OP, INOUT_FIRST, ACC32, RNE, RNE>(src, k, dst, 0, rne_end);
     if (rne_end < count) lp_range<V, BF, OP, INOUT_FIRST, ACC32, RNE, false>(src, k, dst, rne_end, count);
 }

@@ -36,8 +36,8 @@
 #include <cstring>
 #include <type_traits>
 
-#include "../../include/mi_reduce.h"
 #include "host_lp.hpp"
+#include "variant.hpp"  // include/mi_reduce.h and the variant rule shared with the kernels
 
 namespace {
 
@@ -302,7 +302,7 @@ void fold(const void* const* inputs, int k, void* out, size_t count, unsigned v)
     typedef typename HT<Tag>::C C;
     const bool lp = HT<Tag>::lp;
     const bool acc32 = lp && (v & MI_F_ACC_FP32);
-    const uint64_t trunc_from = (count / 16) * 16;
+    const uint64_t trunc_from = mi::tail_trunc_from(count);
     if (!lp && k == 2) {  // ccl_comp_reduce: one pass, out = op(in, inout)
         const C* a = static_cast<const C*>(inputs[0]);
         const C* x = static_cast<const C*>(inputs[1]);
@@ -470,40 +470,6 @@ FoldFn pick(int dt, int op, unsigned v) {
     }
 }
 
-// Variant bits that change results for (dtype, op, k) — the same
-// canonicalisation as the device path (mi_reduce.hip canon_flags).
-unsigned canon(int dt, int op, unsigned f, int k) {
-    const bool mm = op == MI_OP_MIN || op == MI_OP_MAX;
-    switch (dt) {
-        case MI_FLOAT32:
-        case MI_FLOAT64: return mm ? (f & MI_F_MINMAX_INOUT_FIRST) : 0u;
-        case MI_FLOAT16: {
-            unsigned v = (mm ? (f & (MI_F_MINMAX_INOUT_FIRST | MI_F_FP16_NATIVE_MINMAX)) : 0u) | (f & MI_F_ACC_FP32);
-            // a sum/prod step keeps its NaN order; k = 1 its widening, which quiets a signalling NaN
-            if (k == 2 && mm) v &= ~MI_F_ACC_FP32;
-            return v;
-        }
-        case MI_BFLOAT16: {
-            unsigned v = (mm ? (f & MI_F_MINMAX_INOUT_FIRST) : 0u) |
-                         (f & (MI_F_BF16_RNE | MI_F_ACC_FP32 | MI_F_BF16_TAIL_TRUNC16));
-            if (!((v & MI_F_ACC_FP32) && (v & MI_F_BF16_RNE))) v &= ~MI_F_BF16_TAIL_TRUNC16;
-            if (k == 2 && mm && !(v & MI_F_BF16_TAIL_TRUNC16)) v &= ~MI_F_ACC_FP32;
-            return v;
-        }
-        default: return 0u;
-    }
-}
-
-size_t dsize(int dt) {
-    switch (dt) {
-        case MI_INT8: case MI_UINT8: return 1;
-        case MI_INT16: case MI_UINT16: case MI_FLOAT16: case MI_BFLOAT16: return 2;
-        case MI_INT32: case MI_UINT32: case MI_FLOAT32: return 4;
-        case MI_INT64: case MI_UINT64: case MI_FLOAT64: return 8;
-        default: return 0;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -534,16 +500,16 @@ static int fold_fp16_native(FoldFn fn, const void* const* inputs, int k, void* o
 }
 
 int mi_host_reduce(const void* const* inputs, int k, void* out, size_t count, int dtype, int op, unsigned flags) {
-    if (!dsize(dtype)) return MI_E_INVALID;
+    if (!mi::dtype_size(dtype)) return MI_E_INVALID;
     if (op < MI_OP_SUM || op > MI_OP_MAX) return MI_E_INVALID;
     if (k < 1 || k > MI_MAX_INPUTS) return MI_E_INVALID;
     if (count == 0) return 0;
     if (!inputs || !out) return MI_E_INVALID;
     for (int i = 0; i < k; i++)
         if (!inputs[i]) return MI_E_INVALID;
-    const unsigned v = canon(dtype, op, flags, k);
+    const unsigned v = mi::canon_flags(dtype, op, flags, k);
     if (k == 1 && !(v & MI_F_ACC_FP32)) {  // nothing to combine
-        if (out != inputs[0]) memmove(out, inputs[0], count * dsize(dtype));
+        if (out != inputs[0]) memmove(out, inputs[0], count * mi::dtype_size(dtype));
         return 0;
     }
     if (v & MI_F_FP16_NATIVE_MINMAX) {  // fp16 min/max as VMINPH/VMAXPH (avx512fp16 impl)
@@ -599,7 +565,7 @@ int mi_host_convert(const void* src, int src_dtype, void* dst, int dst_dtype, si
     if (src_dtype == MI_FLOAT32 && dst_dtype == MI_BFLOAT16) {
         const float* s = static_cast<const float*>(src);
         uint16_t* d = static_cast<uint16_t*>(dst);
-        const uint64_t trunc_from = (flags & MI_F_BF16_TAIL_TRUNC16) ? (count / 16) * 16 : count;
+        const uint64_t trunc_from = (flags & MI_F_BF16_TAIL_TRUNC16) ? mi::tail_trunc_from(count) : count;
         for (size_t b = 0; b < count; b += kChunk) {
             const size_t n = std::min<size_t>(kChunk, count - b);
             narrow_bf16(s + b, d + b, n, (flags & MI_F_BF16_RNE) | MI_F_BF16_TAIL_TRUNC16, b, trunc_from);
