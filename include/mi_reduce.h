@@ -514,7 +514,9 @@ size_t mi_pointer_lookups(void);
  * staging buffers and already registers them with Level Zero at this point
  * (src/sched/buffer/buffer_cache.cpp:99-104, import_external_pointer);
  * INTEGRATION.md shows the two-line HIP equivalent.  mi_host_unregister must
- * run before the memory is freed.                                          */
+ * run before the memory is freed.  Where HIP cannot pin existing memory
+ * (hipHostRegister refuses it on some virtual machines) mi_host_register
+ * returns HIP's error and the buffer stays pageable: it is staged as before. */
 int mi_host_register(void* ptr, size_t bytes);
 int mi_host_unregister(void* ptr);
 

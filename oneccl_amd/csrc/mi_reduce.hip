@@ -49,6 +49,9 @@ int fail(int code, const char* what) {
 }
 int hip_fail(hipError_t e, const char* what) {
     g_last_error = std::string(what) + ": " + hipGetErrorString(e);
+    // the caller has the error now: HIP also keeps it as the thread's last
+    // error, where the next kernel launch's check would report it as its own
+    (void)hipGetLastError();
     return (int)e;
 }
 #define MI_HIP(call)                                   \

@@ -13,7 +13,7 @@ import pytest
 
 import oracle
 from oneccl_amd import _lib, comp
-from tests.util import BF16, FP32, assert_same, rand_array, wait_os_threads_gone
+from tests.util import BF16, FP32, assert_same, rand_array, require_host_register, wait_os_threads_gone
 
 pytestmark = pytest.mark.gpu
 
@@ -197,6 +197,7 @@ def test_pinned_ends_with_a_pageable_middle_are_not_zero_copy(gpu_dispatch):
     as pinned -- the zero-copy kernel would read unmapped pages.  It is either
     refused (the ends' mappings differ) or recorded pageable and staged; a
     reduce over it then gives the oracle's bits."""
+    require_host_register()
     m = _lib.mi()
     raw, buf = _page_aligned(8 * PAGE)
     p = buf.ctypes.data
@@ -235,6 +236,7 @@ def test_unregistering_a_declared_pinned_buffer_demotes_it(gpu_dispatch, n):
     """mi_host_unregister turns the declared ranges over
     the buffer pageable before unpinning it, so a later reduce on the (still
     valid, now pageable) memory is staged instead of read in place."""
+    require_host_register()
     m = _lib.mi()
     raw_a, a8 = _page_aligned(n * 4)
     raw_b, b8 = _page_aligned(n * 4)
@@ -265,6 +267,7 @@ def test_operand_running_past_a_pinned_allocation_is_staged():
     go to the zero-copy kernel, which would read the pageable pages in place
     and fault the GPU: classify() checks the pinned allocation's extent and
     stages such an operand.  The kinds are asserted before any GPU call."""
+    require_host_register()
     m = _lib.mi()
     raw, buf = _page_aligned(8 * PAGE)
     p = buf.ctypes.data

@@ -15,8 +15,8 @@ import pytest
 import oracle
 from oneccl_amd import _lib, comp
 from tests import kat
-from tests.util import ALL_DTYPES, BF16, DT_NAME, FP16, FP32, FP64, OP_NAME, OPS, assert_same, from_dev, rand_array, to_dev, \
-    wait_os_threads_gone
+from tests.util import ALL_DTYPES, BF16, DT_NAME, FP16, FP32, FP64, OP_NAME, OPS, assert_same, from_dev, rand_array, \
+    require_host_register, to_dev, wait_os_threads_gone
 
 pytestmark = pytest.mark.gpu
 
@@ -430,6 +430,7 @@ def test_cpp_caller_under_host_asan():
 def test_registered_staging_buffer_takes_zero_copy(dt):
     """A pageable staging buffer registered once (what oneCCL's buffer cache
     would do) is classified pinned and reduced in place."""
+    require_host_register()
     import time
     m = _lib.mi()
     n = (64 << 20) // 4 + 3

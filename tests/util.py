@@ -176,6 +176,35 @@ def guards_intact(t, like: np.ndarray, offset_elems: int, guard_seed: int, what:
                                  f"{int(fill[b]):#04x} -> {int(got[b]):#04x}")
 
 
+_host_register_error = None  # "" once a probe registration has worked, else HIP's message
+
+
+def require_host_register() -> None:
+    """Skip the calling test where HIP cannot pin memory the process already
+    has (hipHostRegister refuses it on some virtual machines).  Probed once,
+    on one page, before the test does any work; for tests whose subject is a
+    registered buffer, which pinned allocations (hipHostMalloc) cannot stand
+    in for."""
+    global _host_register_error
+    import pytest
+
+    from oneccl_amd import _lib
+    if _host_register_error is None:
+        m = _lib.mi()
+        raw = np.zeros(2 * 4096, np.uint8)
+        p = raw.ctypes.data + (-raw.ctypes.data) % 4096
+        if m.mi_host_register(p, 4096) == 0:
+            _lib.check(m.mi_host_unregister(p))
+            _host_register_error = ""
+        else:
+            # only HIP's own refusal of a valid page counts as "not supported"
+            msg = m.mi_last_error().decode()
+            assert msg.startswith("hipHostRegister(") and "invalid" in msg, msg
+            _host_register_error = msg
+    if _host_register_error:
+        pytest.skip("hipHostRegister is not supported here")
+
+
 def convert_expected(src: np.ndarray, sdt: int, ddt: int, flags: int) -> np.ndarray:
     """The oracle's fp32 <-> bf16 / fp16 array conversion under mi_convert's
     flags (0x2 RNE, 0x8 the truncated count % 16 tail)."""
