@@ -345,6 +345,41 @@ typedef struct mi_reduce_desc {
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op,
                     unsigned flags, void* stream);
 
+/* n cross-precision accumulates in one dispatch: a trainer's main_grad (fp32)
+ * += scale * wire_grad (bf16 / fp16) over all its parameter tensors, or the
+ * cast of their fp32 results back to bf16 / fp16.  descs[i].in holds count
+ * elements of in_dtype, descs[i].inout count elements of out_dtype; the pairs
+ * are the four of mi_reduce_bcast_mixed, op is MI_OP_SUM.  For every
+ * descriptor with count > 0, descs[i].inout afterwards holds, bit for bit,
+ * what one existing call writes for it alone:
+ *   Widening.  mi_reduce_bcast_mixed_scaled({in}, 1, in_dtype, acc = inout,
+ * {inout}, 1, fp32, count, sum, flags, scale): inout += (float)scale *
+ * widen(in), the product rounded to fp32 before the add, inout the add's first
+ * source, a NaN never multiplied.
+ *   Narrowing.  The same call with acc = NULL and out_dtype: inout is not
+ * read; the rounding is the flags' (trunc_from from the descriptor's count).
+ *   Everything else is as mi_reduce_bcast_mixed_scaled documents.  The results
+ * are those of the n calls in any order, so no inout may overlap another
+ * descriptor's inout, nor any descriptor's in, its own included (the element
+ * sizes differ: no in-place form); each range with its own side's element
+ * size.  Refused before any HIP call, so a refused batch writes nothing, with
+ * a message naming the argument or the descriptor, in this order:
+ * MI_E_UNSUPPORTED for a dtype pair outside the four, then an op other than
+ * sum; MI_E_INVALID for n < 0 (n == 0 returns 0), a NULL list, the scale
+ * (mi_reduce_bcast_scaled's rules), a NULL operand, an address that overflows,
+ * an overlap, a pageable operand (as mi_reduce_batch).  Descriptors with
+ * count == 0 are skipped, their pointers not looked at.  Asynchronous on
+ * `stream`; device or device-visible pinned pointers.  One dispatch per 64
+ * descriptors; a descriptor that takes the element loop (operands not aligned
+ * to their element size, or, under mi_set_unaligned_vectors(0), an input off
+ * the destination's grid), every descriptor under mi_set_max_blocks, and one
+ * of 2^39 elements or more get that existing call's own launch, in batch
+ * order.  mi_version() is unchanged: the symbol's presence is how a caller
+ * detects the entry point.                                                  */
+int mi_reduce_batch_mixed(const mi_reduce_desc_t* descs, int n, int in_dtype,
+                          int out_dtype, int op, unsigned flags, double scale,
+                          void* stream);
+
 /* ---- synchronous, pointer-kind-agnostic entry (what src/comp calls) --- *
  * Same math as mi_reduce, but `in`/`inout` may each be device memory,
  * pinned host memory or pageable host memory; returns only when the result
@@ -585,7 +620,8 @@ int mi_get_residency(int device, int k, int* waves_per_cu, unsigned* lds_bytes);
  * acc = 1 when an accumulator is given, and by the 2-input kernel's plan for
  * two loads and one store per lane (k + acc = 2, m = 1);
  * mi_reduce_bcast_mixed_scaled takes that plan as it is (adopted, its own
- * residencies were not swept).                                              */
+ * residencies were not swept).  mi_reduce_batch_mixed launches under the
+ * 2-input kernel's plan (k = 2) in both directions: adopted, not swept.     */
 int mi_set_residency(int k, int waves_per_cu);
 /* Store policy of mi_reduce_bcast's vector stores (tuning knob): 1 (default)
  * = sc1 + nt, as the 2-input kernel stores (the line leaves L2 as it is

@@ -21,6 +21,7 @@ from .comp import (  # noqa: F401
     fp16_impl,
     impl_types,
     reduce,
+    reduce_batch_mixed,
     reduce_bcast,
     reduce_bcast_mixed,
     reduce_bcast_mixed_scaled,

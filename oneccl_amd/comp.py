@@ -257,6 +257,42 @@ def reduce_bcast_mixed_scaled(inputs: Sequence, outs: Sequence, scale: float, ac
     _mixed("reduce_bcast_mixed_scaled", inputs, outs, acc, flags, stream, scale)
 
 
+def reduce_batch_mixed(pairs: Sequence, scale: float = 1.0, flags: Optional[int] = None, stream=None) -> None:
+    """For every (src, dst) of `pairs`, in one dispatch per 64 pairs
+    (mi_reduce_batch_mixed): dst += scale * src for bf16 or fp16 sources and
+    fp32 destinations (the product rounded to fp32, then one add), or dst =
+    scale * src rounded once for fp32 sources and bf16 or fp16 destinations.
+    One dtype on each side; no dst may overlap another dst or any src.
+    flags=None: reference_flags of the 16-bit dtype."""
+    pairs = [tuple(p) for p in pairs]
+    if not pairs:
+        return
+    s0, d0 = pairs[0]
+    for s, d in pairs:
+        if s.dtype != s0.dtype:
+            raise TypeError(f"all sources must have one dtype ({s.dtype} against {s0.dtype})")
+        if d.dtype != d0.dtype:
+            raise TypeError(f"all destinations must have one dtype ({d.dtype} against {d0.dtype})")
+    idt, odt = _torch_ccl_dtype(s0), _torch_ccl_dtype(d0)
+    lp = (datatype.bfloat16, datatype.float16)
+    if not ((idt in lp and odt == datatype.float32) or (idt == datatype.float32 and odt in lp)):
+        raise TypeError(f"unsupported dtype pair {s0.dtype} -> {d0.dtype}: bf16 / fp16 sources with fp32 destinations, "
+                        "or fp32 sources with bf16 / fp16 destinations")
+    for s, d in pairs:
+        if s.numel() != d.numel():
+            raise ValueError(f"a pair must have the same numel ({s.numel()} against {d.numel()})")
+        if not (s.is_contiguous() and d.is_contiguous()):
+            raise ValueError("tensors must be contiguous")
+        if s.device != s0.device or d.device != s0.device:
+            raise ValueError(f"all tensors must be on one device ({s0.device})")
+    if not s0.is_cuda:
+        raise ValueError("device entry points take device tensors")
+    descs = _lib.desc_array([(s.data_ptr(), d.data_ptr(), s.numel()) for s, d in pairs])
+    f = reference_flags(idt if idt in lp else odt) if flags is None else flags
+    check(mi().mi_reduce_batch_mixed(descs, len(pairs), int(idt), int(odt), int(reduction.sum), f, float(scale),
+                                     _stream_handle(stream)), "mi_reduce_batch_mixed")
+
+
 # ---- the drop-in shim (synchronous, host or device pointers) ------------
 
 def comp_reduce(in_ptr: int, count: int, inout_ptr: int, dtype: datatype, op: reduction) -> Optional[int]:

@@ -1004,11 +1004,8 @@ LaunchMxFn<SC> pick_mixed(int idt, int odt, unsigned v) {
                               : &launch_mixed<float, bf16_tag, V_BF16_RNE, RUNS, SC>;
 }
 
-// The checks the mixed calls make before they look at an operand, in the
-// documented order: the dtype pair, the op, acc against the direction, then
-// check_fanout_lists.
-int check_mixed_lists(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m, int odt,
-                      int op, bool* narrowing_out) {
+// The dtype pair and the op of every cross-precision call, in that order.
+int check_mixed_pair(int idt, int odt, int op, bool* narrowing_out) {
     const bool widening = (idt == MI_BFLOAT16 || idt == MI_FLOAT16) && odt == MI_FLOAT32;
     const bool narrowing = idt == MI_FLOAT32 && (odt == MI_BFLOAT16 || odt == MI_FLOAT16);
     if (!widening && !narrowing)
@@ -1016,9 +1013,25 @@ int check_mixed_lists(const void* const* inputs, int k, int idt, const void* acc
                     "in_dtype/out_dtype: the pairs are bf16->fp32, fp16->fp32, fp32->bf16, fp32->fp16 "
                     "(equal dtypes: mi_reduce_bcast)");
     if (op != MI_OP_SUM) return fail(MI_E_UNSUPPORTED, "op: a mixed-precision reduction is a sum (MI_OP_SUM)");
-    if (acc && narrowing) return fail(MI_E_UNSUPPORTED, "acc: an accumulator is fp32, so only a widening call takes one");
     *narrowing_out = narrowing;
+    return 0;
+}
+
+// The checks the mixed calls make before they look at an operand, in the
+// documented order: the dtype pair, the op, acc against the direction, then
+// check_fanout_lists.
+int check_mixed_lists(const void* const* inputs, int k, int idt, const void* acc, void* const* outs, int m, int odt,
+                      int op, bool* narrowing_out) {
+    if (int rc = check_mixed_pair(idt, odt, op, narrowing_out)) return rc;
+    if (acc && *narrowing_out)
+        return fail(MI_E_UNSUPPORTED, "acc: an accumulator is fp32, so only a widening call takes one");
     return check_fanout_lists(inputs, k, acc, outs, m);
+}
+
+// The variant bits that change a bit of a cross-precision call: the narrowing
+// conversion's (canon_flags); none when widening.
+unsigned mixed_variant(bool narrowing, int odt, int op, unsigned flags, int k) {
+    return narrowing ? (canon_flags(odt, op, flags | V_ACC_FP32, k) & (V_BF16_RNE | V_TAIL_TRUNC)) : 0u;
 }
 
 // What is left of the two mixed calls once their arguments have passed: the
@@ -1030,8 +1043,7 @@ int issue_mixed(const void* const* inputs, int k, int idt, const void* acc, void
     const size_t es_in = dtype_size(idt), es_out = dtype_size(odt);
     if (int rc = require_fanout_visible(inputs, k, count * es_in, acc, count * 4, outs, m, count * es_out)) return rc;
 
-    // the variant bits that change a bit: the narrowing conversion's (canon_flags)
-    const unsigned v = narrowing ? (canon_flags(odt, op, flags | V_ACC_FP32, k) & (V_BF16_RNE | V_TAIL_TRUNC)) : 0u;
+    const unsigned v = mixed_variant(narrowing, odt, op, flags, k);
 
     const MixedGrid g = plan_mixed_grid(es_in, es_out, count, outs, m, inputs, k, acc, unaligned_vectors() != 0);
     MXArgs a = fanout_kargs<MXArgs>(inputs, k, outs, m, count, g);
@@ -1068,39 +1080,54 @@ int launch_reduce_bcast_mixed(const void* const* inputs, int k, int idt, const v
 // descriptor batch: independent 2-input reduces in one launch
 // ---------------------------------------------------------------------------
 // Outputs must be pairwise disjoint and disjoint from other descriptors'
-// inputs, or the result would depend on which tile ran first.
-int check_batch_disjoint(const mi_reduce_desc_t* d, int n, size_t es) {
+// inputs, or the result would depend on which tile ran first.  `in` spans
+// count * es_in bytes and `inout` count * es_io.  With one element size a
+// descriptor's own `in` may overlap its `inout` (mi_reduce's in-place form);
+// across element sizes (mi_reduce_batch_mixed) there is no such form, and its
+// own counts as any other's.
+int check_batch_disjoint(const mi_reduce_desc_t* d, int n, size_t es_in, size_t es_io) {
     struct Rng {
         uintptr_t lo, hi;
         int owner;
     };
+    char msg[160];
     // A range end lo + count * es must not wrap: a corrupt count would
     // otherwise pass the overlap test below with an end below its start.
     for (int i = 0; i < n; i++) {
         if (!d[i].count) continue;
-        const uintptr_t lim = UINTPTR_MAX / es;
         const uintptr_t lo_in = reinterpret_cast<uintptr_t>(d[i].in), lo_io = reinterpret_cast<uintptr_t>(d[i].inout);
-        if (d[i].count > lim || d[i].count * es > UINTPTR_MAX - lo_in || d[i].count * es > UINTPTR_MAX - lo_io)
-            return fail(MI_E_INVALID, "batch descriptor count overflows the address space");
+        const bool in_wraps = d[i].count > UINTPTR_MAX / es_in || d[i].count * es_in > UINTPTR_MAX - lo_in;
+        if (in_wraps || d[i].count > UINTPTR_MAX / es_io || d[i].count * es_io > UINTPTR_MAX - lo_io) {
+            snprintf(msg, sizeof(msg), "descs[%d].%s + count overflows the address space", i, in_wraps ? "in" : "inout");
+            return fail(MI_E_INVALID, msg);
+        }
     }
     std::vector<Rng> outs;
     outs.reserve(n);
     for (int i = 0; i < n; i++)
         if (d[i].count) {
             const uintptr_t lo = reinterpret_cast<uintptr_t>(d[i].inout);
-            outs.push_back({lo, lo + d[i].count * es, i});
+            outs.push_back({lo, lo + d[i].count * es_io, i});
         }
     std::sort(outs.begin(), outs.end(), [](const Rng& x, const Rng& y) { return x.lo < y.lo; });
     for (size_t j = 1; j < outs.size(); j++)
-        if (outs[j].lo < outs[j - 1].hi) return fail(MI_E_INVALID, "batch descriptors' outputs overlap");
+        if (outs[j].lo < outs[j - 1].hi) {
+            snprintf(msg, sizeof(msg), "descs[%d].inout and descs[%d].inout overlap",
+                     std::min(outs[j - 1].owner, outs[j].owner), std::max(outs[j - 1].owner, outs[j].owner));
+            return fail(MI_E_INVALID, msg);
+        }
     // outs are disjoint and sorted, so their ends are sorted too
     for (int i = 0; i < n; i++) {
         if (!d[i].count) continue;
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(d[i].in), hi = lo + d[i].count * es;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(d[i].in), hi = lo + d[i].count * es_in;
         auto it = std::upper_bound(outs.begin(), outs.end(), lo,
                                    [](uintptr_t v, const Rng& r) { return v < r.hi; });
         for (; it != outs.end() && it->lo < hi; ++it)
-            if (it->owner != i) return fail(MI_E_INVALID, "a batch input overlaps another descriptor's output");
+            if (it->owner != i || es_in != es_io) {
+                snprintf(msg, sizeof(msg), "descs[%d].in overlaps descs[%d].inout%s", i, it->owner,
+                         es_in != es_io ? " (no in-place form across element sizes)" : "");
+                return fail(MI_E_INVALID, msg);
+            }
     }
     return 0;
 }
@@ -1119,7 +1146,7 @@ int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsign
         if (int rc = require_gpu_visible(d[i].in, d[i].count * es)) return rc;
         if (int rc = require_gpu_visible(d[i].inout, d[i].count * es)) return rc;
     }
-    if (int rc = check_batch_disjoint(d, n, es)) return rc;
+    if (int rc = check_batch_disjoint(d, n, es, es)) return rc;
     const unsigned v = canon_flags(dt, op, flags, 2);
     const Kern kern = pick(dt, op, v);
     if (!kern.batch) return fail(MI_E_UNSUPPORTED, "no kernel for this dtype/op/variant");
@@ -1156,6 +1183,95 @@ int launch_reduce_batch(const mi_reduce_desc_t* d, int n, int dt, int op, unsign
         a.nvec[j] = g.nvec;
         a.head[j] = (uint8_t)g.head;
         a.tail[j] = (uint8_t)g.tail;
+        a.trunc_from[j] = (count / 16) * 16;
+        a.block0[j] = (uint32_t)blocks;
+        blocks += nb;
+    }
+    return flush();
+}
+
+// ---------------------------------------------------------------------------
+// descriptor batch across precisions (mi_reduce_batch_mixed): n independent
+// mi_reduce_bcast_mixed_scaled calls of one input and one output, widening with
+// the destination as the accumulator, in one launch
+// ---------------------------------------------------------------------------
+typedef hipError_t (*LaunchMbFn)(dim3, hipStream_t, const MBArgs&, const ScaleArg&, unsigned lds);
+
+template <typename ST, typename DT, unsigned V>
+hipError_t launch_mixed_batch(dim3 grid, hipStream_t s, const MBArgs& a, const ScaleArg& sc, unsigned lds) {
+    hipLaunchKernelGGL((mixed_batch_kernel<ST, DT, V, kMixedRuns>), grid, dim3(kMixedBlock), lds, s, a, sc);
+    return hipGetLastError();
+}
+
+LaunchMbFn pick_mixed_batch(int idt, int odt, unsigned v) {  // pick_mixed's six (ST, DT, V)
+    if (idt == MI_BFLOAT16) return &launch_mixed_batch<bf16_tag, float, 0u>;
+    if (idt == MI_FLOAT16) return &launch_mixed_batch<fp16_tag, float, 0u>;
+    if (odt == MI_FLOAT16) return &launch_mixed_batch<float, fp16_tag, 0u>;
+    if (!(v & V_BF16_RNE)) return &launch_mixed_batch<float, bf16_tag, 0u>;
+    return (v & V_TAIL_TRUNC) ? &launch_mixed_batch<float, bf16_tag, V_BF16_RNE | V_TAIL_TRUNC>
+                              : &launch_mixed_batch<float, bf16_tag, V_BF16_RNE>;
+}
+
+int launch_reduce_batch_mixed(const mi_reduce_desc_t* d, int n, int idt, int odt, int op, unsigned flags, double scale,
+                              hipStream_t stream) {
+    bool narrowing;
+    if (int rc = check_mixed_pair(idt, odt, op, &narrowing)) return rc;
+    if (n < 0) return fail(MI_E_INVALID, "n: negative descriptor count");
+    if (n == 0) return 0;
+    if (!d) return fail(MI_E_INVALID, "descs: null descriptor list");
+    ScaleArg sc;
+    if (int rc = check_scale(MI_FLOAT32, scale, &sc)) return rc;
+    char msg[96];
+    for (int i = 0; i < n; i++)
+        if (d[i].count && (!d[i].in || !d[i].inout)) {
+            snprintf(msg, sizeof(msg), "descs[%d].%s is NULL", i, d[i].in ? "inout" : "in");
+            return fail(MI_E_INVALID, msg);
+        }
+    const size_t es_in = dtype_size(idt), es_out = dtype_size(odt);
+    if (int rc = check_batch_disjoint(d, n, es_in, es_out)) return rc;
+    for (int i = 0; i < n; i++) {
+        if (!d[i].count) continue;
+        if (int rc = require_gpu_visible(d[i].in, d[i].count * es_in)) return rc;
+        if (int rc = require_gpu_visible(d[i].inout, d[i].count * es_out)) return rc;
+    }
+    const LaunchMbFn kern = pick_mixed_batch(idt, odt, mixed_variant(narrowing, odt, op, flags, 1));
+
+    const uint64_t te = mixed_tile_elems<kMixedRuns>();
+    MBArgs a;
+    memset(&a, 0, sizeof(a));
+    uint64_t blocks = 0;
+    auto flush = [&]() -> int {
+        if (!a.n) return 0;
+        a.block0[a.n] = (uint32_t)blocks;
+        a.store_sc1 = g_bcast_store.load(std::memory_order_relaxed);
+        // two loads and one store per lane: the 2-input kernel's plan, as mi_reduce_bcast_mixed takes for them
+        const hipError_t e = kern(dim3((unsigned)blocks), stream, a, sc, wave_cap_lds(stream, planned_waves(2)));
+        if (e != hipSuccess) return hip_fail(e, "kernel launch");
+        memset(&a, 0, sizeof(a));
+        blocks = 0;
+        return 0;
+    };
+    for (int i = 0; i < n; i++) {
+        const size_t count = d[i].count;
+        if (!count) continue;
+        const void* const in1 = d[i].in;
+        void* const out1 = d[i].inout;
+        const void* const acc = narrowing ? nullptr : out1;
+        const MixedGrid g = plan_mixed_grid(es_in, es_out, count, &out1, 1, &in1, 1, acc, unaligned_vectors() != 0);
+        const uint64_t nb = std::max<uint64_t>((g.ngroups * 8 + te - 1) / te, 1);
+        if (!g.vec || max_blocks() != 0 || nb > 0x40000000ull) {  // element loop / grid knob / huge: own launch
+            if (int rc = launch_reduce_bcast_mixed<ScaleArg>(&in1, 1, idt, acc, &out1, 1, odt, count, op, flags, scale,
+                                                             stream))
+                return rc;
+            continue;
+        }
+        if (a.n == kBatchMax || blocks + nb > 0x7FFFFFFFull)
+            if (int rc = flush()) return rc;
+        const int j = a.n++;
+        a.src[j] = in1;
+        a.dst[j] = out1;
+        a.ngroups[j] = g.ngroups;
+        a.edge[j] = (uint32_t)g.head | (uint32_t)g.tail << 8;
         a.trunc_from[j] = (count / 16) * 16;
         a.block0[j] = (uint32_t)blocks;
         blocks += nb;
@@ -2361,6 +2477,13 @@ int mi_reduce_bcast_mixed_scaled(const void* const* inputs, int k, int in_dtype,
 int mi_reduce_batch(const mi_reduce_desc_t* descs, int n, int dtype, int op, unsigned flags,
                     void* stream) {
     return guarded([&]() -> int { return launch_reduce_batch(descs, n, dtype, op, flags, (hipStream_t)stream); });
+}
+
+int mi_reduce_batch_mixed(const mi_reduce_desc_t* descs, int n, int in_dtype, int out_dtype, int op, unsigned flags,
+                          double scale, void* stream) {
+    return guarded([&]() -> int {
+        return launch_reduce_batch_mixed(descs, n, in_dtype, out_dtype, op, flags, scale, (hipStream_t)stream);
+    });
 }
 
 namespace {

@@ -1797,6 +1797,114 @@ __global__ __launch_bounds__(kMixedBlock) void mixed_scaled_stride_kernel(MXArgs
     mixed_stride<ST, DT, V, RUNS>(a, sc);
 }
 
+// ---------------------------------------------------------------------------
+// Descriptor-batched cross-precision accumulate (mi_reduce_batch_mixed): up to
+// kBatchMax independent (src, dst) pairs in one launch, dst in the other
+// element size.  Widening, dst += s * widen(src) (mx_scaled_onto, dst as the
+// accumulator); narrowing, dst = narrow(s * src) and dst is not read.  Each is
+// mixed_scaled_kernel's result for one input and one output, bit for bit.
+//   Every descriptor lies on its own destination's 16-byte grid
+// (plan_mixed_grid per descriptor): its own scalar head (< 16 elements) and
+// tail (< 8), a body of groups of 8 elements cut into the mixed tile (64 * RUNS
+// runs of 4 in the lane layout above), and its own trunc_from.  Block b works
+// on descriptor d = the last one with block0[d] <= b, tile b - block0[d]: the
+// binary search runs on blockIdx and kernel arguments only, so it stays on
+// scalar registers and the pointers it finds are wave-uniform (one buffer
+// descriptor per stream and tile, no waterfall; lanes carry 32-bit offsets).
+// A descriptor's first block also does its head and tail (head_tail against
+// the descriptor's tile index, not the grid's block 0).
+//   Two loads (one when narrowing) and one store per lane, the 2-input
+// kernel's regime; both loads are issued before the first combine.  The fast
+// fold has no NaN fix-ups; the screen on the words as loaded sends a run with
+// an Inf or NaN in src (or dst, widening) through the X = true refold.  No LDS.
+//   The argument block: 4 x 512 bytes of pointers, groups and trunc_from, 260
+// of block0, 256 of heads and tails (one dword per descriptor: scalar loads
+// have no byte form, and a byte table costs a vector load and a readfirstlane
+// ahead of the tile), two ints: 2576 bytes, and ScaleArg's 16 after it, of
+// the 4 KiB a kernel's arguments may take.
+// ---------------------------------------------------------------------------
+struct MBArgs {
+    const void* src[kBatchMax];
+    void* dst[kBatchMax];
+    uint64_t ngroups[kBatchMax];                // groups of 8 elements in the body
+    uint64_t trunc_from[kBatchMax];             // V_TAIL_TRUNC threshold (element index in the descriptor)
+    uint32_t block0[kBatchMax + 1];             // first block of each descriptor; [n] = grid size
+    uint32_t edge[kBatchMax];                   // scalar elements: head (< 16) | tail (< 8) << 8
+    int n;
+    int store_sc1;                              // stores sc1 + nt instead of nt (mi_set_bcast_store)
+};
+
+template <typename ST, typename DT, unsigned V, int RUNS>
+__global__ __launch_bounds__(kMixedBlock) void mixed_batch_kernel(MBArgs a, ScaleArg sc) {
+    using SS = typename Tr<ST>::S;
+    using DS = typename Tr<DT>::S;
+    constexpr bool WIDE = std::is_same<DT, float>::value;
+    constexpr uint32_t TE = mixed_tile_elems<RUNS>();
+    const uint32_t b = blockIdx.x;
+    int lo = 0, hi = a.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (a.block0[mid] <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const void* const src = a.src[lo];
+    void* const dst = a.dst[lo];
+    const uint64_t nbody = a.ngroups[lo] * 8, trunc_from = a.trunc_from[lo];
+    const uint32_t edge = a.edge[lo], head = edge & 0xFFu, tail = edge >> 8, tile = b - a.block0[lo];
+
+    // The scalar path is mixed_elem itself, on this descriptor as a k = 1,
+    // m = 1 call (only the fields it reads for that are set).
+    head_tail(tile, head, tail, head + nbody, [&](uint64_t i) {
+        MXArgs e;
+        e.in[0] = src;
+        e.out[0] = dst;
+        e.acc = WIDE ? dst : nullptr;
+        e.trunc_from = trunc_from;
+        e.k = 1;
+        e.m = 1;
+        mixed_elem<ST, DT, V>(e, i, sc);
+    });
+
+    const uint64_t t0 = (uint64_t)tile * TE;
+    const uint64_t left = nbody > t0 ? nbody - t0 : 0;
+    const uint32_t ne = (uint32_t)(left < (uint64_t)TE ? left : (uint64_t)TE);  // a multiple of 8
+    if (ne == 0) return;
+    const uint64_t first = head + t0;
+
+    const __amdgpu_buffer_rsrc_t srs = tile_rsrc(src, first * sizeof(SS), ne * (uint32_t)sizeof(SS));
+    const __amdgpu_buffer_rsrc_t drs = tile_rsrc(dst, first * sizeof(DS), ne * (uint32_t)sizeof(DS));
+    typename MxRun<ST>::type x[RUNS][1];
+    u32x4 xa[RUNS];
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) x[r][0] = mx_load<ST>(srs, mx_off(r, sizeof(SS)));
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) {
+        if constexpr (WIDE) xa[r] = __builtin_amdgcn_raw_buffer_load_b128(drs, mx_off(r, 4), 0, kAuxNT);
+        else xa[r] = u32x4{0u, 0u, 0u, 0u};
+    }
+
+    typename MxRun<DT>::type res[RUNS];
+#pragma unroll
+    for (int r = 0; r < RUNS; r++) {
+        const uint64_t e0 = first + (uint64_t)(r * kMixedBlock + threadIdx.x) * 4u;
+        res[r] = mx_fold<ST, DT, V, false, 1>(x[r], 1, WIDE, xa[r], e0, trunc_from, sc);
+        const bool hit = mx_inf_nan<ST>(x[r][0]) || (WIDE && mx_inf_nan<float>(xa[r]));
+        if (__builtin_expect(hit, 0)) res[r] = mx_fold<ST, DT, V, true, 1>(x[r], 1, WIDE, xa[r], e0, trunc_from, sc);
+    }
+
+    const auto store = [&](auto aux) {
+#pragma unroll
+        for (int r = 0; r < RUNS; r++) {
+            if constexpr (sizeof(DS) == 2)
+                __builtin_amdgcn_raw_buffer_store_b64(res[r], drs, mx_off(r, 2), 0, decltype(aux)::value);
+            else
+                __builtin_amdgcn_raw_buffer_store_b128(res[r], drs, mx_off(r, 4), 0, decltype(aux)::value);
+        }
+    };
+    if (a.store_sc1) store(std::integral_constant<int, kAuxSC1NT>());
+    else store(std::integral_constant<int, kAuxNT>());
+}
+
 // Byte copy with optional non-temporal stores (ccl_comp_copy), on the
 // destination's 16-byte grid: block 0 copies the < 16-byte head and tail byte
 // by byte, the body moves 16-byte vectors.  The source may sit at any byte
